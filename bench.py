@@ -11,7 +11,16 @@ library default; --pipes 1 for one launch per step).  N=1 runs configs[2]
 chains) and gathers the kept posterior states to rank 0 over RCCL at the
 end of the timed region (the checkpoint).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--full] [--dump-outputs DIR]
+
+A plain run does only what the headline needs: set-up, W warm-up steps, the K
+timed steps, the result line.  --full adds the legs that take runs of their
+own: the CPU baseline of the reference's solver (before the GPU is touched;
+--no-cpu-baseline drops it) and the fp64 record (--f64-steps timed steps of a
+--precision 64 sampler after the timed region; --f64-steps 0 drops it).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy
+(`dump_outputs`); the inputs are seeded, so two builds given the same
+arguments can be compared array for array.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py starts the N
 ranks itself (torch.distributed.run on 127.0.0.1, one process per GPU, before
@@ -355,6 +364,45 @@ def f64_record(p, v0, per_gpu, args, dev, stream):
             "ms_per_step": round(elapsed / args.f64_steps * 1e3, 2), "roofline": rl}
 
 
+# ---------------------------------------------------------------- outputs
+DUMP_MODEL_BYTES = 28 << 20     # cap of v.npy and of posterior.npy (the other arrays are a few MB): under 64 MB in all
+DUMP_SEED = 2016
+
+
+def dump_chains(nchains, ncell):
+    """The chains whose models --dump-outputs writes: all of them while
+    [nchains, ncell] float32 fits DUMP_MODEL_BYTES, else a fixed (seeded)
+    sorted sample of that many."""
+    k = max(1, min(nchains, DUMP_MODEL_BYTES // (4 * ncell)))
+    if k == nchains:
+        return np.arange(nchains)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(nchains, size=k, replace=False))
+
+
+def dump_outputs(out_dir, post, smp):
+    """--dump-outputs: what the timed path left after its last step, as
+    DIR/<name>.npy -- `v` (float32; the chains' models after the last step,
+    rows `chains`), `logl` (float64) and `naccept` of every chain, the last
+    step's forward: `ttab` (float32 travel times [chains, stations, events]),
+    `niter` and `accept`, and `posterior` (float32; the kept states the timed
+    checkpoint wrote to `post` -- those of the first timed step, as keepK =
+    --steps -- rows `chains`).  Models are integers below 2^24, so float32
+    holds them exactly.  Rank 0 writes (N > 1: its own shard, and its rows
+    of the gathered posterior)."""
+    ttab, niter, acc = smp.last()
+    v, logl, nacc, _ = smp.state()
+    rows = dump_chains(v.shape[0], v[0].size)
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"v": v.reshape(v.shape[0], -1)[rows].astype(np.float32),
+              "posterior": post.cpu().numpy()[rows].astype(np.float32),
+              "chains": rows.astype(np.float64),
+              "logl": logl.astype(np.float64), "naccept": nacc.astype(np.float64),
+              "ttab": ttab.astype(np.float32), "niter": niter.astype(np.float32),
+              "accept": acc.astype(np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 
 # ---------------------------------------------------------------- main
 def main():
@@ -364,6 +412,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="C3")
     ap.add_argument("--chains", type=int, default=0, help="chains per GPU (default: the config's)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baseline and the fp64 record (a plain run: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-cores", type=int, default=0)
     ap.add_argument("--cpu-rounds", type=int, default=CPU_ROUNDS)
@@ -374,7 +426,7 @@ def main():
     ap.add_argument("--max-waves", type=int, default=0,
                     help="cap on the resident FSM waves per launch (0 = occupancy x CUs; experiments)")
     ap.add_argument("--f64-steps", type=int, default=2,
-                    help="timed steps of the appended fp64 record (one GPU, --precision 32 runs; 0 = none)")
+                    help="timed steps of --full's fp64 record (one GPU, --precision 32 runs; 0 = none)")
     ap.add_argument("--f64-warmup", type=int, default=1)
     ap.add_argument("--pipes", type=int, default=2, choices=(1, 2, 3, 4),
                     help="the sampler's chains as two halves on two streams (the library default, DESIGN.md "
@@ -399,8 +451,11 @@ def main():
     rank = int(os.environ.get("RANK", 0))
     local_rank = int(os.environ.get("LOCAL_RANK", 0))
     if args.probe_ranks:
-        print(json.dumps({"probe": "rank", "rank": rank, "world": world, "local_rank": local_rank,
-                          "gpus": args.gpus}), flush=True)
+        # one write per line: the ranks share the launcher's stdout, and a line
+        # written apart from its newline can land inside another rank's
+        sys.stdout.write(json.dumps({"probe": "rank", "rank": rank, "world": world, "local_rank": local_rank,
+                                     "gpus": args.gpus}) + "\n")
+        sys.stdout.flush()
         return 0
     # MCEIK_BENCH_REHEARSAL=1: rehearse the N > 1 flow on ONE GPU (every rank on
     # device 0, torch.distributed over gloo, host-side gather; RCCL takes one
@@ -421,7 +476,7 @@ def main():
     lo, hi = mcmc.shard(per_gpu * world, rank, world)
     v0 = mcmc.initial_models(p, range(lo, hi))
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = core_share(cpu_baseline(p, v0[0], args.cpu_cores or cpu_cores(), args.cpu_rounds))
 
     import torch
@@ -532,9 +587,11 @@ def main():
     stats = smp.fsm_stats()
     info = smp.info()
     _, logl, nacc, _ = smp.state()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, post, smp)
     smp.close()
     f64 = None
-    if world == 1 and args.precision == 32 and args.f64_steps > 0:
+    if args.full and world == 1 and args.precision == 32 and args.f64_steps > 0:
         f64 = f64_record(p, v0, per_gpu, args, dev, stream)
 
     if rank == 0:

@@ -78,6 +78,26 @@ def test_gpus_n_launches_n_ranks():
     assert r1.returncode == 0 and [json.loads(l)["world"] for l in r1.stdout.splitlines()] == [1]
 
 
+def test_dump_chains_are_a_fixed_bounded_sample():
+    """--dump-outputs writes every chain's model while they fit the cap, else
+    the same sorted sample on every run; v.npy and posterior.npy stay under the cap."""
+    import numpy as np
+    import bench
+    assert np.array_equal(bench.dump_chains(8, 4096), np.arange(8))
+    ncell = 32 ** 3                                             # C3: 128^3 nodes, nref 4
+    rows = bench.dump_chains(1024, ncell)
+    assert np.array_equal(rows, bench.dump_chains(1024, ncell))
+    assert len(rows) == 224 and len(set(rows.tolist())) == 224 and np.all(np.diff(rows) > 0)
+    assert 0 <= rows[0] and rows[-1] < 1024
+    assert len(rows) * ncell * 4 <= bench.DUMP_MODEL_BYTES < 30 << 20       # x2 (v, posterior) + a few MB < 64 MB
+    assert len(bench.dump_chains(2, 64 ** 3 * 64)) == 1         # never empty
+
+
+def test_full_and_dump_outputs_are_options():
+    r = _run_bench(["--help"])
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
 def test_world_size_must_equal_gpus():
     """Under an external launcher WORLD_SIZE must equal --gpus (the driver's
     SCALE line would otherwise mislabel its rank count)."""

@@ -26,5 +26,5 @@ timeout -k 10 200 rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCL
     --kernel-include-regex "relocate_lds_kernel" -d "$O/reloc_pmc" -o pmc --output-format csv -- \
     python3 tools/bench_relocate.py --iters 2 > "$O/relocate_pmc.log" 2>&1
 fi
-timeout -k 10 420 python3 bench.py > "$O/bench_default.log" 2>&1
+timeout -k 10 420 python3 bench.py --full > "$O/bench_default.log" 2>&1
 echo done > "$O/DONE"

@@ -19,7 +19,7 @@ SQ2="SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ
 if [ "${M_TRACE:-1}" = 1 ]; then
 echo "[measure_r04] trace"
 timeout -k 10 480 rocprofv3 --kernel-trace --stats -d "$O/trace" -o trace --output-format csv -- \
-    python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --f64-steps 2 > "$O/bench_under_trace.log" 2>&1
+    python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --f64-steps 2 > "$O/bench_under_trace.log" 2>&1
 fi
 for prec in ${M_PRECS:-32 64}; do
   if [ $prec = 32 ]; then K=fsm16_solve_kernel; else K="fsm_solve_kernel<double, 2, true"; fi

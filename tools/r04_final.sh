@@ -10,7 +10,7 @@ trap 'kill $HB 2>/dev/null || true' EXIT
 echo "[r04_final] smoke"
 timeout -k 10 300 python3 -u -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1
 echo "[r04_final] bench"
-timeout -k 10 500 python3 -u bench.py > "$O/bench.log" 2>&1
+timeout -k 10 500 python3 -u bench.py --full > "$O/bench.log" 2>&1
 echo "[r04_final] trace"
 timeout -k 10 500 rocprofv3 --kernel-trace --stats -d "$O/trace" -o trace --output-format csv -- \
     python3 bench.py --no-cpu-baseline > "$O/bench_under_trace.log" 2>&1

@@ -14,7 +14,7 @@ timeout -k 10 1500 python3 -u -m pytest -x -v -s --timeout 1200 --timeout-method
 echo "[r05] rehearsal --gpus 2"
 MCEIK_BENCH_REHEARSAL=1 timeout -k 10 400 python3 bench.py --gpus 2 --steps 2 --warmup 1 > "$O/bench_rehearsal_n2.log" 2>&1
 echo "[r05] bench"
-timeout -k 10 500 python3 -u bench.py ${F_BENCH:-} > "$O/bench.log" 2>&1
+timeout -k 10 500 python3 -u bench.py --full ${F_BENCH:-} > "$O/bench.log" 2>&1
 
 if [ -n "${F_ADMIT:-}" ]; then
   # admission statistics (experiment build mceik_amd/exp/lib_admit.so, one-pipe launch)

@@ -11,7 +11,7 @@ HB=$!
 trap 'kill $HB 2>/dev/null || true' EXIT
 if [[ $P == *s* ]]; then echo "[r05c] smoke"; timeout -k 10 300 python3 -u -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1; fi
 if [[ $P == *t* ]]; then echo "[r05c] tests"; timeout -k 10 1200 python3 -u -m pytest -x -v --timeout 600 --timeout-method thread -m gpu tests > "$O/gpu_tests.log" 2>&1; fi
-if [[ $P == *b* ]]; then echo "[r05c] bench"; timeout -k 10 500 python3 -u bench.py > "$O/bench.log" 2>&1; fi
+if [[ $P == *b* ]]; then echo "[r05c] bench"; timeout -k 10 500 python3 -u bench.py --full > "$O/bench.log" 2>&1; fi
 if [[ $P == *r* ]]; then
   echo "[r05c] trace"
   timeout -k 10 500 rocprofv3 --kernel-trace --stats -d "$O/trace" -o trace --output-format csv -- \

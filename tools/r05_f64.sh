@@ -13,7 +13,7 @@ timeout -k 10 600 python3 -u -m pytest -x -v --timeout 300 --timeout-method thre
 echo "[r05f] full suite"
 timeout -k 10 1200 python3 -u -m pytest -x -v --timeout 600 --timeout-method thread -m gpu tests > "$O/gpu_tests.log" 2>&1
 echo "[r05f] bench"
-timeout -k 10 500 python3 -u bench.py > "$O/bench.log" 2>&1
+timeout -k 10 500 python3 -u bench.py --full > "$O/bench.log" 2>&1
 if [ -n "${F_AB:-}" ]; then
   echo "[r05f] fp64 A/B"
   cp mceik_amd/libmceik_hip.so /tmp/lib_keep.so

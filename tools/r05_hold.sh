@@ -14,7 +14,7 @@ echo "[r05h] full suite"
 timeout -k 10 1200 python3 -u -m pytest -x -v --timeout 600 --timeout-method thread -m gpu tests \
     > "$O/gpu_tests.log" 2>&1
 echo "[r05h] bench"
-timeout -k 10 500 python3 -u bench.py > "$O/bench.log" 2>&1
+timeout -k 10 500 python3 -u bench.py --full > "$O/bench.log" 2>&1
 if [ -n "${F_AB:-}" ]; then
   echo "[r05h] A/B"
   AB_VARIANTS="hold0 hold1" AB_ROUNDS=2 AB_ARGS="--steps 3 --warmup 1 --f64-steps 0" timeout -k 10 900 bash tools/ab_bench.sh

@@ -18,5 +18,5 @@ AB_VARIANTS="${F_VARIANTS:-zf0 zf1}" AB_ROUNDS=2 AB_ARGS="--precision 64 --steps
     timeout -k 10 600 bash tools/ab_bench.sh
 mv gpurun_out/ab "$O/ab64"
 echo "[r05zf] bench"
-timeout -k 10 500 python3 -u bench.py > "$O/bench.log" 2>&1
+timeout -k 10 500 python3 -u bench.py --full > "$O/bench.log" 2>&1
 echo done > "$O/DONE"

@@ -21,6 +21,6 @@ timeout -k 10 1000 python3 -u -m pytest -x -v -s --timeout 900 --timeout-method 
 fi
 if [ "${A_BENCH:-1}" = 1 ]; then
 echo "[r06_a] bench"
-timeout -k 10 400 python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --f64-steps 1 > "$O/bench.log" 2>&1
+timeout -k 10 400 python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --f64-steps 1 > "$O/bench.log" 2>&1
 fi
 echo done > "$O/DONE"

@@ -18,10 +18,10 @@ echo "[r06_final] smoke"
 timeout -k 10 300 python3 -u -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1
 fi
 echo "[r06_final] bench (driver arguments)"
-timeout -k 10 600 python3 -u bench.py --gpus 1 --steps 20 --warmup 5 > "$O/bench.log" 2>&1
+timeout -k 10 600 python3 -u bench.py --full --gpus 1 --steps 20 --warmup 5 > "$O/bench.log" 2>&1
 echo "[r06_final] bench under the kernel trace"
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$O/trace" -o trace --output-format csv -- \
-    python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --f64-steps 2 > "$O/bench_under_trace.log" 2>&1
+    python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --f64-steps 2 > "$O/bench_under_trace.log" 2>&1
 if [ "${E_CONFIGS:-1}" = 1 ]; then
 echo "[r06_final] C2 / C5"
 timeout -k 10 300 python3 bench.py --config C2 --steps 10 --warmup 1 --no-cpu-baseline --f64-steps 0 > "$O/bench_c2.log" 2>&1
