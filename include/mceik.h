@@ -154,6 +154,71 @@ int mceik_mcmc_fsm_stats(mceik_mcmc *s, double *fsm_ms, long long *nlaunch, unsi
 int mceik_mcmc_fsm_solves(mceik_mcmc *s, unsigned long long *solves);
 int mceik_mcmc_finalize(mceik_mcmc **s);
 
+/* ---- streaming posterior (csrc/posterior.hip) -------------
+ * A run's kept states do not fit anywhere at production sizes, so a sampler
+ * can summarise them as it goes.  Cell velocities are integers: per model
+ * entry (ncm = nphase * ncell of them) the sampler keeps the exact integer
+ * sums of v and v^2 over the accumulated states and a histogram, so the
+ * result does not depend on the order of accumulation and shards or ranks
+ * merge by plain addition.  Off by default; with it off nothing changes.
+ *
+ * per_chain = 1: sum, sumsq are [nchains][ncm] (needed for R-hat; 16 bytes per
+ * chain and entry).  per_chain = 0: [ncm], pooled over the chains.  nbins in
+ * [0, 128]: hist is [ncm][nbins] uint32 pooled over the chains (0: none; a
+ * count wraps past 2^32 - 1 = nchains x states); a value v of phase ph falls
+ * in bin clamp((long long)(v - lo) * nbins / (hi - lo + 1), 0, nbins - 1),
+ * (lo, hi) = (vmin, vmax) for P and (vsmin, vsmax) for S, in integers.
+ *
+ * While enabled, mceik_mcmc_run adds every chain's state after step gs when
+ * gs >= nburnIn && (gs - nburnIn) % keepK == 0 -- the rule of the kept states,
+ * whatever max_samples is (0 included) -- by a kernel queued behind the
+ * step: no host synchronisation.  The chains are bit for bit those of a run
+ * with the posterior off.  Cost with multi-step launches
+ * (mceik_mcmc_info.multi_step): a launch then ends right after the next kept
+ * step: keepK = 1 means one step per launch (C2: -18% proposals/s, keepK = 8
+ * -4%); a large keepK adds one launch boundary per kept step.
+ *
+ * Every function returns 0, 1 on invalid arguments (posterior not enabled,
+ * nbins out of range, partials that do not match) or -1 on a device failure. */
+typedef struct mceik_posterior_opts { int per_chain; int nbins; } mceik_posterior_opts;
+typedef struct mceik_posterior_partials {      /* caller-allocated host arrays */
+    int ncm, nbins, per_chain;
+    long long nchains, nkept;                  /* chains summed, states per chain */
+    long long *S;                              /* [ncm] sum over chains of sum */
+    unsigned long long *Q, *P;                 /* [ncm][2] = lo, hi words: sum over chains of sumsq, of sum^2 */
+    unsigned long long *hist;                  /* [ncm][nbins], widened for merging */
+} mceik_posterior_partials;
+/* Allocates and zeroes the accumulators; on an enabled sampler: resets them
+ * (with other options: reallocates). */
+int mceik_mcmc_posterior_enable(mceik_mcmc *s, const mceik_posterior_opts *o);
+int mceik_mcmc_posterior_disable(mceik_mcmc *s);
+/* Adds the chains' current state now (enqueued on the sampler's stream). */
+int mceik_mcmc_posterior_accumulate(mceik_mcmc *s);
+/* Host copies of / replacements for the accumulators (checkpoints): n states
+ * per chain, sum and sumsq [nchains][ncm] or [ncm], hist [ncm][nbins].  get
+ * synchronises, any pointer may be NULL; set needs sum, sumsq, and hist when
+ * nbins > 0. */
+int mceik_mcmc_posterior_get(mceik_mcmc *s, long long *n, long long *sum, long long *sumsq, unsigned *hist);
+int mceik_mcmc_posterior_set(mceik_mcmc *s, long long n, const long long *sum, const long long *sumsq,
+                             const unsigned *hist);
+/* The chain axis summed on the device into exact partials: S = sum_c sum_c,
+ * Q = sum_c sumsq_c, P = sum_c sum_c^2 (128 bits; pooled mode: P = 0).  Fills
+ * every scalar of *out and the arrays it points to (hist only when nbins > 0).
+ * Synchronises. */
+int mceik_mcmc_posterior_partials(mceik_mcmc *s, mceik_posterior_partials *out);
+/* Host only (no GPU call).  merge: dst += src; 1 unless ncm, nbins, per_chain
+ * and nkept agree.  finish: with M = nchains, n = nkept, N = M n every
+ * numerator is an exact 128-bit integer converted to double once, then
+ *   mean = S / N,   var = (N Q - S^2) / (N (N - 1)),
+ *   W = (n Q - P) / (M n (n - 1)),   B/n = (M P - S^2) / (M (M - 1) n^2),
+ *   rhat = sqrt(((n - 1)/n W + B/n) / W)
+ * (pooled sample variance; Gelman-Rubin potential scale reduction).  rhat is
+ * NaN when per_chain = 0, M < 2, n < 2 or the W numerator is 0 (no variance
+ * within any chain); var is NaN when N < 2, mean when N = 0.  mean, var, rhat:
+ * [ncm], any may be NULL. */
+int mceik_posterior_merge(mceik_posterior_partials *dst, const mceik_posterior_partials *src);
+int mceik_posterior_finish(const mceik_posterior_partials *p, double *mean, double *var, double *rhat);
+
 /* ---- multi-rank runs (one process per GPU; csrc/comm.hip) ---------------
  * The sampler's only collective is the checkpoint gather (SURVEY s.8e) over
  * RCCL (xGMI on one node).  Bootstrap as RCCL's: rank 0 calls

@@ -87,6 +87,18 @@ class McmcInfo(C.Structure):
                 ("multi_step", C.c_int)]
 
 
+class PosteriorOpts(C.Structure):
+    """mceik_posterior_opts (include/mceik.h)."""
+    _fields_ = [("per_chain", C.c_int), ("nbins", C.c_int)]
+
+
+class PosteriorPartials(C.Structure):
+    """mceik_posterior_partials (include/mceik.h): caller-allocated host arrays."""
+    _fields_ = [("ncm", C.c_int), ("nbins", C.c_int), ("per_chain", C.c_int),
+                ("nchains", C.c_longlong), ("nkept", C.c_longlong),
+                ("S", C.c_void_p), ("Q", C.c_void_p), ("P", C.c_void_p), ("hist", C.c_void_p)]
+
+
 # every extern "C" symbol include/*.h declares
 EXPORTS = ("eikonal3d_serial_driver", "eikonal3d_serial_driver_sp", "eikonal3d_batch_solve", "eikonal3d_initialize", "eikonal3d_solve",
            "eikonal3d_finalize", "locate3d_gridsearch__double64", "locate3d_gridsearch__float64",
@@ -100,6 +112,9 @@ EXPORTS = ("eikonal3d_serial_driver", "eikonal3d_serial_driver_sp", "eikonal3d_b
            "mceik_mcmc_get_state", "mceik_mcmc_get_samples", "mceik_mcmc_last", "mceik_mcmc_fsm_stats",
            "mceik_mcmc_checkpoint", "mceik_mcmc_restore", "mceik_mcmc_finalize", "mceik_mcmc_last_phase",
            "mceik_mcmc_get_info", "mceik_mcmc_fsm_solves",
+           "mceik_mcmc_posterior_enable", "mceik_mcmc_posterior_disable", "mceik_mcmc_posterior_accumulate",
+           "mceik_mcmc_posterior_get", "mceik_mcmc_posterior_set", "mceik_mcmc_posterior_partials",
+           "mceik_posterior_merge", "mceik_posterior_finish",
            "mceik_parms_defaults", "mceik_parms_set", "mceik_parms_read", "mceik_parms_args", "mceik_parms_write",
            "mceik_comm_available", "mceik_comm_unique_id", "mceik_comm_init", "mceik_comm_finalize", "mceik_mcmc_gather",
            "os_path_exists", "os_path_isdir", "os_path_isfile", "os_makedirs", "os_mkdir")
@@ -191,5 +206,21 @@ def lib():
     L.mceik_mcmc_get_info.argtypes = [C.c_void_p, C.POINTER(McmcInfo)]
     L.mceik_mcmc_finalize.restype = C.c_int
     L.mceik_mcmc_finalize.argtypes = [C.POINTER(C.c_void_p)]
+    L.mceik_mcmc_posterior_enable.restype = C.c_int
+    L.mceik_mcmc_posterior_enable.argtypes = [C.c_void_p, C.POINTER(PosteriorOpts)]
+    L.mceik_mcmc_posterior_disable.restype = C.c_int
+    L.mceik_mcmc_posterior_disable.argtypes = [C.c_void_p]
+    L.mceik_mcmc_posterior_accumulate.restype = C.c_int
+    L.mceik_mcmc_posterior_accumulate.argtypes = [C.c_void_p]
+    L.mceik_mcmc_posterior_get.restype = C.c_int
+    L.mceik_mcmc_posterior_get.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)] + [C.c_void_p] * 3
+    L.mceik_mcmc_posterior_set.restype = C.c_int
+    L.mceik_mcmc_posterior_set.argtypes = [C.c_void_p, C.c_longlong] + [C.c_void_p] * 3
+    L.mceik_mcmc_posterior_partials.restype = C.c_int
+    L.mceik_mcmc_posterior_partials.argtypes = [C.c_void_p, C.POINTER(PosteriorPartials)]
+    L.mceik_posterior_merge.restype = C.c_int
+    L.mceik_posterior_merge.argtypes = [C.POINTER(PosteriorPartials), C.POINTER(PosteriorPartials)]
+    L.mceik_posterior_finish.restype = C.c_int
+    L.mceik_posterior_finish.argtypes = [C.POINTER(PosteriorPartials)] + [C.c_void_p] * 3
     _lib = L
     return L

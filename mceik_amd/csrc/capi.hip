@@ -20,6 +20,7 @@
 #include "mcmc_common.h"
 #include "fsm_single.h"
 #include "rccl_rt.h"
+#include "posterior.h"
 
 hipError_t fsm_launch(const FsmLaunch &L, int is_double, int nwaves, hipStream_t st);
 hipError_t fsm_zero_words(unsigned *p, int n, hipStream_t st);
@@ -1546,6 +1547,7 @@ struct mceik_mcmc {
     int device, max_samples, nburn, keepk, nkept, niter_total;
     int nkept_base;                    // nkept at the last restore: earlier states are not in the ring
     long long step;
+    McmcPost *post;                    // streaming posterior accumulators (posterior.hip), or null
     hipStream_t stream;
     void *ws;
     size_t ws_bytes;
@@ -2102,6 +2104,30 @@ extern "C" int mceik_mcmc_set_stream(mceik_mcmc *s, void *stream)
     return 0;
 }
 
+// The keep rule of the kept states and of the posterior: step gs is kept when
+// gs >= nburnIn && (gs - nburnIn) % keepK == 0.
+static bool kept_step(const mceik_mcmc *s, long long gs)
+{
+    return gs >= s->nburn && (gs - s->nburn) % s->keepk == 0;
+}
+
+static long long next_kept_step(const mceik_mcmc *s)     // the first kept step >= s->step
+{
+    if (s->step < s->nburn) return s->nburn;
+    const long long r = (s->step - s->nburn) % s->keepk;
+    return r ? s->step + s->keepk - r : s->step;
+}
+
+int mcmc_post_ctx(mceik_mcmc *s, McmcPostCtx *out)
+{
+    if (!s || !out) return 1;
+    out->device = s->device;
+    out->stream = s->stream;
+    out->D = &s->D;
+    out->slot = &s->post;
+    return 0;
+}
+
 // Steps of one call.  Returns -1 on a HIP failure; the caller joins the pipes
 // whatever happened, so the caller's stream is always ordered after every
 // kernel this call queued on the internal streams.
@@ -2111,7 +2137,10 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
         // the first step's proposals here, then up to MCEIK_MC_CHUNK steps per
         // FSM launch (the kernel accepts, keeps and proposes the rest)
         for (int done = 0; done < nsteps;) {
-            const int n = std::min(nsteps - done, MCEIK_MC_CHUNK);
+            int n = std::min(nsteps - done, MCEIK_MC_CHUNK);
+            // posterior on: the launch ends right after the next kept step, when
+            // every chain's current state is its state after that step
+            if (s->post) n = (int)std::min<long long>(n, next_kept_step(s) - s->step + 1);
             McmcExt x;
             x.dev = s->d_dev; x.sync = s->d_sync; x.spin_limit = s->spin_limit;
             x.step0 = (int)s->step; x.nsteps = n;
@@ -2120,6 +2149,10 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
             if (mcmc_forward(s, true, -1, &x)) return -1;
             for (int i = 0; i < n; i++, s->step++)
                 if (s->max_samples && s->step >= s->nburn && (s->step - s->nburn) % s->keepk == 0) s->nkept++;
+            if (s->post && kept_step(s, s->step - 1)) {
+                HIPCHK(mcmc_post_accumulate(s->post, s->D, 0, s->stream));
+                mcmc_post_counted(s->post);
+            }
             if (s->report) clock_report(s, "steps");
             done += n;
         }
@@ -2129,6 +2162,7 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
     for (int i = 0; i < nsteps; i++) {
         uint64_t step = (uint64_t)s->step;
         int slot = -1;
+        const bool post = s->post && kept_step(s, s->step);
         if (s->max_samples && s->step >= s->nburn && (s->step - s->nburn) % s->keepk == 0) {
             slot = s->nkept % s->max_samples;
             s->nkept++;
@@ -2138,12 +2172,17 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
                 HIPCHK(mcmc_propose(s->pD[k], step, s->pst[k]));
                 if (mcmc_forward(s, true, k)) return -1;
                 HIPCHK(mcmc_accept(s->pD[k], slot, s->pst[k]));
+                if (post)           // the pipe's rows of the accumulators, offset like its keep_v (dev_view)
+                    HIPCHK(mcmc_post_accumulate(s->post, s->pD[k], s->pD[k].chain_offset - s->D.chain_offset,
+                                                s->pst[k]));
             }
         } else {
             HIPCHK(mcmc_propose(s->D, step, s->stream));
             if (mcmc_forward(s, true)) return -1;
             HIPCHK(mcmc_accept(s->D, slot, s->stream));
+            if (post) HIPCHK(mcmc_post_accumulate(s->post, s->D, 0, s->stream));
         }
+        if (post) mcmc_post_counted(s->post);
         if (s->report) clock_report(s, "step");
         s->step++;
     }
@@ -2426,6 +2465,7 @@ extern "C" int mceik_mcmc_finalize(mceik_mcmc **ps)
     if (s->pfork) hipEventDestroy(s->pfork);
     for (int k = 0; k < MCEIK_MAX_PIPES; k++) if (s->pws_own[k] && s->pws[k]) hipFree(s->pws[k]);
     for (void *p : s->allocs) hipFree(p);
+    mcmc_post_free(s->post);
     for (int i = 0; i < 2 * s->ev_made; i++) hipEventDestroy(s->ev[i]);
     if (s->ws) hipFree(s->ws);
     delete s;

@@ -355,6 +355,7 @@ class Sampler:
         self._L = L
         self.max_samples = int(max_samples)
         self._last_full = True          # the last forward solved every model (init / restore)
+        self._post = None               # (per_chain, nbins) while the streaming posterior is enabled
 
     @property
     def model_shape(self):
@@ -440,8 +441,11 @@ class Sampler:
         if self._L.mceik_mcmc_checkpoint(self._h, v.ctypes.data_as(C.c_void_p), logl.ctypes.data_as(C.c_void_p),
                                          nacc.ctypes.data_as(C.c_void_p), C.byref(step), C.byref(nkept)) != 0:
             raise RuntimeError("mceik_mcmc_checkpoint failed")
-        return {"v": v, "logl": logl, "naccept": nacc, "step": step.value, "nkept": nkept.value,
-                "chain_offset": self.chain_offset, "seed": self.p.seed}
+        ck = {"v": v, "logl": logl, "naccept": nacc, "step": step.value, "nkept": nkept.value,
+              "chain_offset": self.chain_offset, "seed": self.p.seed}
+        if self._post is not None:       # the accumulators belong to the state of a run that summarises itself
+            ck["posterior"] = self.posterior_raw()
+        return ck
 
     def restore(self, ck, recompute_logl=False):
         """Load a checkpoint() dict (mceik_mcmc_restore)."""
@@ -458,6 +462,81 @@ class Sampler:
             raise RuntimeError(f"mceik_mcmc_restore failed ({rc})")
         if recompute_logl:
             self._last_full = True
+        if "posterior" in ck and self._post is not None:
+            self._posterior_set(ck["posterior"])
+
+    # --- streaming posterior (include/mceik.h mceik_mcmc_posterior_*) ---
+    def posterior_enable(self, per_chain=True, nbins=64):
+        """Start (or reset) the streaming posterior: exact integer sums of v and
+        v^2 per model entry over the kept steps of run() -- per chain (R-hat
+        needs that; 16 bytes per chain and entry) or pooled over the chains --
+        and a pooled histogram of `nbins` <= 128 bins over the prior range (0:
+        none).  Works with max_samples = 0; the chains do not change."""
+        o = _lib.PosteriorOpts(int(bool(per_chain)), int(nbins))
+        rc = self._L.mceik_mcmc_posterior_enable(self._h, C.byref(o))
+        if rc != 0:
+            raise (ValueError if rc == 1 else RuntimeError)(f"mceik_mcmc_posterior_enable failed ({rc}): nbins in [0, 128]")
+        self._post = (bool(per_chain), int(nbins))
+
+    def posterior_disable(self):
+        if self._L.mceik_mcmc_posterior_disable(self._h) != 0:
+            raise RuntimeError("mceik_mcmc_posterior_disable failed")
+        self._post = None
+
+    def _posterior_on(self):
+        if self._post is None:
+            raise RuntimeError("the posterior is not enabled (Sampler.posterior_enable)")
+        return self._post
+
+    def posterior_accumulate(self):
+        """Add the chains' current state to the accumulators now (enqueued)."""
+        self._posterior_on()
+        rc = self._L.mceik_mcmc_posterior_accumulate(self._h)
+        if rc != 0:
+            raise RuntimeError(f"mceik_mcmc_posterior_accumulate failed ({rc})")
+
+    def posterior_raw(self):
+        """The accumulators as host arrays: {"n": states per chain, "sum", "sumsq":
+        int64 shaped like model_shape (per chain) or model_shape[1:] (pooled),
+        "hist": uint32 model_shape[1:] + (nbins,), "per_chain", "nbins"}."""
+        per_chain, nbins = self._posterior_on()
+        shape = self.model_shape if per_chain else self.model_shape[1:]
+        sm, sq = np.empty(shape, np.int64), np.empty(shape, np.int64)
+        hist = np.empty(self.model_shape[1:] + (nbins,), np.uint32)
+        n = C.c_longlong(0)
+        rc = self._L.mceik_mcmc_posterior_get(self._h, C.byref(n), sm.ctypes.data_as(C.c_void_p),
+                                              sq.ctypes.data_as(C.c_void_p), hist.ctypes.data_as(C.c_void_p))
+        if rc != 0:
+            raise RuntimeError(f"mceik_mcmc_posterior_get failed ({rc})")
+        return {"n": n.value, "sum": sm, "sumsq": sq, "hist": hist, "per_chain": per_chain, "nbins": nbins}
+
+    def _posterior_set(self, raw):
+        per_chain, nbins = self._posterior_on()
+        if bool(raw["per_chain"]) != per_chain or int(raw["nbins"]) != nbins:
+            raise ValueError("the checkpoint's posterior was accumulated with other options")
+        shape = self.model_shape if per_chain else self.model_shape[1:]
+        sm = np.ascontiguousarray(raw["sum"], dtype=np.int64)
+        sq = np.ascontiguousarray(raw["sumsq"], dtype=np.int64)
+        hist = np.ascontiguousarray(raw["hist"], dtype=np.uint32)
+        assert sm.shape == shape and sq.shape == shape and hist.shape == self.model_shape[1:] + (nbins,)
+        rc = self._L.mceik_mcmc_posterior_set(self._h, int(raw["n"]), sm.ctypes.data_as(C.c_void_p),
+                                              sq.ctypes.data_as(C.c_void_p), hist.ctypes.data_as(C.c_void_p))
+        if rc != 0:
+            raise RuntimeError(f"mceik_mcmc_posterior_set failed ({rc})")
+
+    def posterior_partials(self):
+        """The chain axis summed on the GPU into exact partials
+        (`PosteriorPartials`): what ranks exchange and merge."""
+        per_chain, nbins = self._posterior_on()
+        p = self.p
+        bounds = [(p.vmin, p.vmax), (p.vsmin, p.vsmax)][:p.nphase]
+        out = PosteriorPartials(p.nphase * p.ncell, nbins, per_chain, shape=self.model_shape[1:], bounds=bounds)
+        st = out._struct()
+        rc = self._L.mceik_mcmc_posterior_partials(self._h, C.byref(st))
+        if rc != 0:
+            raise RuntimeError(f"mceik_mcmc_posterior_partials failed ({rc})")
+        out.nchains, out.nkept = int(st.nchains), int(st.nkept)
+        return out
 
     def fsm_stats(self, reset=False):
         """(FSM kernel ms from hipEvents, launches, executed iterations summed over
@@ -499,6 +578,115 @@ class Sampler:
             self.close()
         except Exception:
             pass
+
+
+class PosteriorPartials:
+    """Host arrays of mceik_posterior_partials (include/mceik.h): per model
+    entry S = sum_c sum_c (int64 [ncm]), Q = sum_c sumsq_c and P = sum_c sum_c^2
+    (uint64 [ncm, 2]: lo, hi words of 128 bits) and the histogram widened to
+    uint64 [ncm, nbins], over `nchains` chains of `nkept` states each.  Exact
+    integers: partials of shards or ranks merge by addition, in any order.
+    Plain attributes, so it travels as a host object (pickle)."""
+
+    def __init__(self, ncm, nbins, per_chain, nchains=0, nkept=0, shape=None, bounds=None):
+        self.ncm, self.nbins, self.per_chain = int(ncm), int(nbins), bool(per_chain)
+        self.nchains, self.nkept = int(nchains), int(nkept)
+        self.shape = tuple(shape) if shape is not None else (self.ncm,)
+        self.bounds = [tuple(b) for b in bounds] if bounds is not None else None   # per phase (lo, hi) of the bins
+        self.S = np.zeros(self.ncm, np.int64)
+        self.Q = np.zeros((self.ncm, 2), np.uint64)
+        self.P = np.zeros((self.ncm, 2), np.uint64)
+        self.hist = np.zeros((self.ncm, self.nbins), np.uint64)
+
+    def _struct(self):
+        st = _lib.PosteriorPartials()
+        st.ncm, st.nbins, st.per_chain = self.ncm, self.nbins, int(self.per_chain)
+        st.nchains, st.nkept = self.nchains, self.nkept
+        st.S, st.Q, st.P = self.S.ctypes.data, self.Q.ctypes.data, self.P.ctypes.data
+        st.hist = self.hist.ctypes.data if self.nbins else None
+        return st
+
+    def merge(self, other):
+        """self += other (mceik_posterior_merge); both must hold the same
+        entries, bins, mode and states per chain."""
+        a, b = self._struct(), other._struct()
+        rc = _lib.lib().mceik_posterior_merge(C.byref(a), C.byref(b))
+        if rc != 0:
+            raise ValueError("posterior partials do not match (ncm, nbins, per_chain, nkept)")
+        self.nchains = int(a.nchains)
+        return self
+
+    def finish(self):
+        """(mean, var, rhat) float64 [ncm] (mceik_posterior_finish)."""
+        mean, var, rhat = (np.empty(self.ncm, np.float64) for _ in range(3))
+        st = self._struct()
+        rc = _lib.lib().mceik_posterior_finish(C.byref(st), mean.ctypes.data_as(C.c_void_p),
+                                               var.ctypes.data_as(C.c_void_p), rhat.ctypes.data_as(C.c_void_p))
+        if rc != 0:
+            raise RuntimeError(f"mceik_posterior_finish failed ({rc})")
+        return mean, var, rhat
+
+
+class PosteriorSummary:
+    """Posterior of the velocity models from merged `PosteriorPartials`:
+    `mean`, `var` (sample variance over all chains and states), `rhat`
+    (Gelman-Rubin; NaN in pooled mode, with fewer than 2 chains or states, and
+    where no chain moved) shaped like one chain's model, `hist` [..., nbins]
+    uint64, `count` states per chain over `nchains` chains."""
+
+    def __init__(self, parts: PosteriorPartials):
+        mean, var, rhat = parts.finish()
+        sh = parts.shape
+        self.mean, self.var, self.rhat = mean.reshape(sh), var.reshape(sh), rhat.reshape(sh)
+        self.hist = parts.hist.reshape(sh + (parts.nbins,)).copy()
+        self.count, self.nchains, self.nbins = parts.nkept, parts.nchains, parts.nbins
+        self.bounds = parts.bounds
+
+    def quantile(self, q):
+        """Marginal q-quantile (0 <= q <= 1) of every model entry, in numpy from
+        the histogram: the bin where the cumulative count reaches q x total,
+        then linear inside that bin, whose edges are lo + b (hi - lo + 1) /
+        nbins of the phase's prior range.  Its resolution is the bin width; an
+        entry without counts gives NaN."""
+        if not self.nbins or self.bounds is None:
+            raise ValueError("quantile needs a histogram (nbins > 0) and the prior bounds")
+        if not 0.0 <= q <= 1.0:
+            raise ValueError("q in [0, 1]")
+        h = self.hist.astype(np.float64)
+        cum = np.cumsum(h, axis=-1)
+        total = cum[..., -1]
+        target = q * total
+        b = np.minimum((cum < target[..., None]).sum(-1), self.nbins - 1)
+        hb = np.take_along_axis(h, b[..., None], -1)[..., 0]
+        below = np.take_along_axis(cum, b[..., None], -1)[..., 0] - hb
+        frac = np.divide(target - below, hb, out=np.zeros_like(hb), where=hb > 0)
+        lo = np.empty(self.mean.shape)
+        width = np.empty(self.mean.shape)
+        for ph, (l, u) in enumerate(self.bounds):
+            sel = (ph,) if len(self.bounds) > 1 else ()
+            lo[sel] = l
+            width[sel] = (u - l + 1) / self.nbins
+        out = lo + (b + frac) * width
+        return np.where(total > 0, out, np.nan)
+
+
+def posterior_summary(smp: Sampler, group=None, dst=0):
+    """`PosteriorSummary` of a sampler's streaming posterior.  With a
+    torch.distributed `group` (one process per GPU, each with its chain shard)
+    the ranks' exact partials are gathered as host objects and merged on rank
+    `dst`, which gets the summary of all chains; the other ranks get None."""
+    parts = smp.posterior_partials()
+    if group is not None:
+        import torch.distributed as dist
+        rank, world = dist.get_rank(group), dist.get_world_size(group)
+        every = [None] * world if rank == dst else None
+        dist.gather_object(parts, every, dst=dst, group=group)
+        if rank != dst:
+            return None
+        parts = every[0]
+        for other in every[1:]:
+            parts.merge(other)
+    return PosteriorSummary(parts)
 
 
 def picks_from_forward(device=0, precision=64):
