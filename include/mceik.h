@@ -219,6 +219,57 @@ int mceik_mcmc_posterior_partials(mceik_mcmc *s, mceik_posterior_partials *out);
 int mceik_posterior_merge(mceik_posterior_partials *dst, const mceik_posterior_partials *src);
 int mceik_posterior_finish(const mceik_posterior_partials *p, double *mean, double *var, double *rhat);
 
+/* ---- parallel tempering / replica exchange (csrc/temper.hip)
+ * Off by default; with it off nothing changes.  A sampler of nchains chains
+ * and ntemps rungs (nchains % ntemps == 0) holds G = nchains / ntemps replica
+ * groups; rung r of group g is local chain r * G + g, so the cold chains
+ * (beta = 1) are the local chains [0, G) = the global chains chain_offset +
+ * [0, G).  Groups never span ranks.  A chain index never changes its rung:
+ * swaps exchange states, not temperatures, so kept samples, get_state, gather,
+ * naccept and per-chain posterior rows keep their meaning (cold = the first G
+ * chains of each shard; naccept[c] counts at chain c's temperature).
+ *
+ * Ladder: beta[ntemps] with beta[0] == 1.0 exactly and 0 < beta[r+1] <=
+ * beta[r]; ntemps = 1 is the untempered sampler.  Chain c accepts a proposal
+ * inside the prior iff log u < beta[c / G] * (logL' - logL) (one fp64
+ * multiply; the uniform prior is not tempered).
+ *
+ * Swaps: with K = swap_every > 0, before the proposal of global step gs > 0
+ * with gs % K == 0 a swap round runs; it belongs to step gs (a checkpoint
+ * taken at step == gs has not done it, the resumed run does it first).
+ * parity = (gs / K) & 1; every group g and rung r with r % 2 == parity and
+ * r + 1 < ntemps forms the pair a = r * G + g, b = a + G, draws Philox4x32-10
+ * with counter {(uint32)gs, (uint32)(gs >> 32), 1, 0} and key {chain_offset +
+ * a, seed} (the proposals use counter word 2 = 0), log u = log((out[0] + 0.5)
+ * / 2^32) by the sampler's deterministic log, and swaps iff
+ *   log u < (beta[r] - beta[r+1]) * (logL[b] - logL[a]).
+ * A swap exchanges the two chains' models, logL and the hidden state that
+ * goes with them; naccept stays.  attempts[r] / accepts[r] count per rung pair.
+ * Both kernels are queued on the sampler's stream: no host synchronisation.
+ * With multi-step launches (mceik_mcmc_info.multi_step) a launch ends before
+ * the next swap step.
+ *
+ * While tempering is on the streaming posterior sees the cold chains only
+ * (partials.nchains = G; the accumulators keep their [nchains][ncm] shape, the
+ * hot rows stay zero); enable / disable return 1 while an enabled posterior
+ * holds states.  The kept ring and mceik_mcmc_gather keep every chain.
+ *
+ * Every function returns 0, 1 on invalid arguments (not enabled, parity not 0
+ * or 1, a bad ladder, nchains % ntemps != 0) or -1 on a device failure. */
+typedef struct mceik_temper_opts { int ntemps; int swap_every; const double *beta; } mceik_temper_opts;
+/* Turns tempering on (or replaces the ladder); resets the counters. */
+int mceik_mcmc_temper_enable(mceik_mcmc *s, const mceik_temper_opts *o);
+int mceik_mcmc_temper_disable(mceik_mcmc *s);
+/* The options in force; beta [ntemps] or NULL. */
+int mceik_mcmc_temper_get(mceik_mcmc *s, int *ntemps, int *swap_every, double *beta);
+/* attempts, accepts [ntemps - 1] (either may be NULL).  Synchronises. */
+int mceik_mcmc_temper_stats(mceik_mcmc *s, long long *attempts, long long *accepts, int reset);
+/* One swap round now, Philox counter = the current step; enqueued. */
+int mceik_mcmc_temper_swap(mceik_mcmc *s, int parity);
+/* Host only: the geometric ladder beta[r] = tmax^(-r / (ntemps - 1)), beta[0]
+ * = 1 exactly (ntemps >= 1, finite tmax >= 1, else 1). */
+int mceik_temper_ladder(int ntemps, double tmax, double *beta);
+
 /* ---- multi-rank runs (one process per GPU; csrc/comm.hip) ---------------
  * The sampler's only collective is the checkpoint gather (SURVEY s.8e) over
  * RCCL (xGMI on one node).  Bootstrap as RCCL's: rank 0 calls

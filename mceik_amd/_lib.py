@@ -99,6 +99,11 @@ class PosteriorPartials(C.Structure):
                 ("S", C.c_void_p), ("Q", C.c_void_p), ("P", C.c_void_p), ("hist", C.c_void_p)]
 
 
+class TemperOpts(C.Structure):
+    """mceik_temper_opts (include/mceik.h)."""
+    _fields_ = [("ntemps", C.c_int), ("swap_every", C.c_int), ("beta", C.c_void_p)]
+
+
 # every extern "C" symbol include/*.h declares
 EXPORTS = ("eikonal3d_serial_driver", "eikonal3d_serial_driver_sp", "eikonal3d_batch_solve", "eikonal3d_initialize", "eikonal3d_solve",
            "eikonal3d_finalize", "locate3d_gridsearch__double64", "locate3d_gridsearch__float64",
@@ -115,6 +120,8 @@ EXPORTS = ("eikonal3d_serial_driver", "eikonal3d_serial_driver_sp", "eikonal3d_b
            "mceik_mcmc_posterior_enable", "mceik_mcmc_posterior_disable", "mceik_mcmc_posterior_accumulate",
            "mceik_mcmc_posterior_get", "mceik_mcmc_posterior_set", "mceik_mcmc_posterior_partials",
            "mceik_posterior_merge", "mceik_posterior_finish",
+           "mceik_mcmc_temper_enable", "mceik_mcmc_temper_disable", "mceik_mcmc_temper_get",
+           "mceik_mcmc_temper_stats", "mceik_mcmc_temper_swap", "mceik_temper_ladder",
            "mceik_parms_defaults", "mceik_parms_set", "mceik_parms_read", "mceik_parms_args", "mceik_parms_write",
            "mceik_comm_available", "mceik_comm_unique_id", "mceik_comm_init", "mceik_comm_finalize", "mceik_mcmc_gather",
            "os_path_exists", "os_path_isdir", "os_path_isfile", "os_makedirs", "os_mkdir")
@@ -222,5 +229,17 @@ def lib():
     L.mceik_posterior_merge.argtypes = [C.POINTER(PosteriorPartials), C.POINTER(PosteriorPartials)]
     L.mceik_posterior_finish.restype = C.c_int
     L.mceik_posterior_finish.argtypes = [C.POINTER(PosteriorPartials)] + [C.c_void_p] * 3
+    L.mceik_mcmc_temper_enable.restype = C.c_int
+    L.mceik_mcmc_temper_enable.argtypes = [C.c_void_p, C.POINTER(TemperOpts)]
+    L.mceik_mcmc_temper_disable.restype = C.c_int
+    L.mceik_mcmc_temper_disable.argtypes = [C.c_void_p]
+    L.mceik_mcmc_temper_get.restype = C.c_int
+    L.mceik_mcmc_temper_get.argtypes = [C.c_void_p, pi, pi, C.c_void_p]
+    L.mceik_mcmc_temper_stats.restype = C.c_int
+    L.mceik_mcmc_temper_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.mceik_mcmc_temper_swap.restype = C.c_int
+    L.mceik_mcmc_temper_swap.argtypes = [C.c_void_p, C.c_int]
+    L.mceik_temper_ladder.restype = C.c_int
+    L.mceik_temper_ladder.argtypes = [C.c_int, C.c_double, C.c_void_p]
     _lib = L
     return L

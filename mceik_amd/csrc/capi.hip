@@ -21,6 +21,7 @@
 #include "fsm_single.h"
 #include "rccl_rt.h"
 #include "posterior.h"
+#include "temper.h"
 
 hipError_t fsm_launch(const FsmLaunch &L, int is_double, int nwaves, hipStream_t st);
 hipError_t fsm_zero_words(unsigned *p, int n, hipStream_t st);
@@ -1548,6 +1549,15 @@ struct mceik_mcmc {
     int nkept_base;                    // nkept at the last restore: earlier states are not in the ring
     long long step;
     McmcPost *post;                    // streaming posterior accumulators (posterior.hip), or null
+    // Parallel tempering (temper.hip); ntemps = 0: off.  Rung r
+    // of replica group g is chain r * G + g (G = nchains / ntemps), so the cold
+    // chains are [0, G).  Before the proposal of step gs > 0 with gs %
+    // swap_every == 0 a swap round of parity (gs / swap_every) & 1 runs.
+    int ntemps, swap_every;
+    std::vector<double> beta;          // the ladder [ntemps]
+    double *d_beta;                    // [nchains] the chains' beta (D.beta while ntemps > 1)
+    int *d_tflag;                      // [nchains] the round's swap flag per pair
+    unsigned long long *d_tcnt;        // [2][nchains] attempts, accepts per rung pair
     hipStream_t stream;
     void *ws;
     size_t ws_bytes;
@@ -1705,6 +1715,7 @@ static McmcDev dev_view(const McmcDev &D, int off, int n)
     if (V.ttab_cur) V.ttab_cur += o * D.nphase * D.nstat * D.nev;
     if (V.keep_v) V.keep_v += oc;
     if (V.keep_logl) V.keep_logl += o;
+    if (V.beta) V.beta += o;
     return V;
 }
 
@@ -2111,6 +2122,9 @@ static bool kept_step(const mceik_mcmc *s, long long gs)
     return gs >= s->nburn && (gs - s->nburn) % s->keepk == 0;
 }
 
+// Chains the streaming posterior sees: the cold ones while tempering is on.
+static int temper_cold(const mceik_mcmc *s) { return s->ntemps > 0 ? s->D.nchains / s->ntemps : s->D.nchains; }
+
 static long long next_kept_step(const mceik_mcmc *s)     // the first kept step >= s->step
 {
     if (s->step < s->nburn) return s->nburn;
@@ -2125,6 +2139,32 @@ int mcmc_post_ctx(mceik_mcmc *s, McmcPostCtx *out)
     out->stream = s->stream;
     out->D = &s->D;
     out->slot = &s->post;
+    out->ncold = temper_cold(s);
+    return 0;
+}
+
+// The posterior sees the cold chains only: view V (chains [off, off +
+// V.nchains) of the sampler) intersected with [0, G).
+static hipError_t post_add(mceik_mcmc *s, const McmcDev &V, int off, hipStream_t st)
+{
+    const int G = temper_cold(s);
+    if (off >= G) return hipSuccess;
+    if (off + V.nchains <= G) return mcmc_post_accumulate(s->post, V, off, st);
+    McmcDev W = V;
+    W.nchains = G - off;
+    return mcmc_post_accumulate(s->post, W, off, st);
+}
+
+// A swap round belongs to step gs and runs before its proposal.
+static bool swap_step(const mceik_mcmc *s, long long gs)
+{
+    return s->ntemps > 1 && s->swap_every > 0 && gs > 0 && gs % s->swap_every == 0;
+}
+
+static int temper_round(mceik_mcmc *s, int parity)
+{
+    HIPCHK(temper_swap_round(s->D, s->ntemps, parity, (uint64_t)s->step, s->d_tflag, s->d_tcnt,
+                             s->d_tcnt + s->D.nchains, s->stream));
     return 0;
 }
 
@@ -2141,6 +2181,10 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
             // posterior on: the launch ends right after the next kept step, when
             // every chain's current state is its state after that step
             if (s->post) n = (int)std::min<long long>(n, next_kept_step(s) - s->step + 1);
+            // tempering: this step's swap round first; the launch ends before the next one
+            if (swap_step(s, s->step) && temper_round(s, (int)((s->step / s->swap_every) & 1))) return -1;
+            if (s->ntemps > 1 && s->swap_every > 0)
+                n = (int)std::min<long long>(n, (s->step / s->swap_every + 1) * s->swap_every - s->step);
             McmcExt x;
             x.dev = s->d_dev; x.sync = s->d_sync; x.spin_limit = s->spin_limit;
             x.step0 = (int)s->step; x.nsteps = n;
@@ -2150,7 +2194,7 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
             for (int i = 0; i < n; i++, s->step++)
                 if (s->max_samples && s->step >= s->nburn && (s->step - s->nburn) % s->keepk == 0) s->nkept++;
             if (s->post && kept_step(s, s->step - 1)) {
-                HIPCHK(mcmc_post_accumulate(s->post, s->D, 0, s->stream));
+                HIPCHK(post_add(s, s->D, 0, s->stream));
                 mcmc_post_counted(s->post);
             }
             if (s->report) clock_report(s, "steps");
@@ -2167,20 +2211,32 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
             slot = s->nkept % s->max_samples;
             s->nkept++;
         }
+        if (swap_step(s, s->step)) {
+            // one round for the whole sampler on its own stream: the pipes join it
+            // and fork again (their split need not fall on a group boundary)
+            for (int k = 0; k < np && np > 1; k++) {
+                HIPCHK(hipEventRecord(s->pjoin[k], s->pst[k]));
+                HIPCHK(hipStreamWaitEvent(s->stream, s->pjoin[k], 0));
+            }
+            if (temper_round(s, (int)((s->step / s->swap_every) & 1))) return -1;
+            if (np > 1) {
+                HIPCHK(hipEventRecord(s->pfork, s->stream));
+                for (int k = 0; k < np; k++) HIPCHK(hipStreamWaitEvent(s->pst[k], s->pfork, 0));
+            }
+        }
         if (np > 1) {
             for (int k = 0; k < np; k++) {
                 HIPCHK(mcmc_propose(s->pD[k], step, s->pst[k]));
                 if (mcmc_forward(s, true, k)) return -1;
                 HIPCHK(mcmc_accept(s->pD[k], slot, s->pst[k]));
                 if (post)           // the pipe's rows of the accumulators, offset like its keep_v (dev_view)
-                    HIPCHK(mcmc_post_accumulate(s->post, s->pD[k], s->pD[k].chain_offset - s->D.chain_offset,
-                                                s->pst[k]));
+                    HIPCHK(post_add(s, s->pD[k], s->pD[k].chain_offset - s->D.chain_offset, s->pst[k]));
             }
         } else {
             HIPCHK(mcmc_propose(s->D, step, s->stream));
             if (mcmc_forward(s, true)) return -1;
             HIPCHK(mcmc_accept(s->D, slot, s->stream));
-            if (post) HIPCHK(mcmc_post_accumulate(s->post, s->D, 0, s->stream));
+            if (post) HIPCHK(post_add(s, s->D, 0, s->stream));
         }
         if (post) mcmc_post_counted(s->post);
         if (s->report) clock_report(s, "step");
@@ -2214,6 +2270,95 @@ extern "C" int mceik_mcmc_run(mceik_mcmc *s, int nsteps)
         }
     }
     return rc;
+}
+
+// ---------------------------------------------------------------------------
+// parallel tempering (include/mceik.h mceik_mcmc_temper_*)
+
+// D.beta changed: the pipes' views and a multi-step sampler's device copy follow.
+static int temper_publish(mceik_mcmc *s)
+{
+    const int nch = s->D.nchains, np = s->npipe;
+    for (int k = 0; k < np && np > 1; k++) {
+        const int lo = (int)((long long)nch * k / np);
+        s->pD[k].beta = s->D.beta ? s->D.beta + lo : nullptr;
+    }
+    if (s->d_dev) HIPCHK(hipMemcpy(s->d_dev, &s->D, sizeof(McmcDev), hipMemcpyHostToDevice));
+    return 0;
+}
+
+extern "C" int mceik_temper_ladder(int ntemps, double tmax, double *beta)
+{
+    if (ntemps < 1 || !beta || !(tmax >= 1.0) || !(tmax <= DBL_MAX)) return 1;
+    beta[0] = 1.0;
+    for (int r = 1; r < ntemps; r++) beta[r] = pow(tmax, -(double)r / (double)(ntemps - 1));
+    return 0;
+}
+
+extern "C" int mceik_mcmc_temper_enable(mceik_mcmc *s, const mceik_temper_opts *o)
+{
+    if (!s || !o || !o->beta || o->ntemps < 1 || o->swap_every < 0) return 1;
+    const int nch = s->D.nchains, nt = o->ntemps;
+    if (nch % nt != 0 || o->beta[0] != 1.0) return 1;
+    for (int r = 0; r + 1 < nt; r++)
+        if (!(o->beta[r + 1] > 0.0 && o->beta[r + 1] <= o->beta[r])) return 1;
+    if (s->post && mcmc_post_count(s->post) > 0) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    if (!s->d_beta && (dalloc(s, &s->d_beta, nch) || dalloc(s, &s->d_tflag, nch) || dalloc(s, &s->d_tcnt, 2 * (size_t)nch)))
+        return -1;
+    const int G = nch / nt;
+    std::vector<double> bc(nch);
+    for (int c = 0; c < nch; c++) bc[c] = o->beta[c / G];
+    HIPCHK(hipMemcpy(s->d_beta, bc.data(), (size_t)nch * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(s->d_tcnt, 0, 2 * (size_t)nch * 8));
+    s->beta.assign(o->beta, o->beta + nt);
+    s->ntemps = nt;
+    s->swap_every = o->swap_every;
+    s->D.beta = nt > 1 ? s->d_beta : nullptr;       // one rung is the untempered sampler
+    return temper_publish(s);
+}
+
+extern "C" int mceik_mcmc_temper_disable(mceik_mcmc *s)
+{
+    if (!s) return 1;
+    if (!s->ntemps) return 0;
+    if (s->post && mcmc_post_count(s->post) > 0) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    s->ntemps = 0;
+    s->swap_every = 0;
+    s->beta.clear();
+    s->D.beta = nullptr;
+    return temper_publish(s);
+}
+
+extern "C" int mceik_mcmc_temper_get(mceik_mcmc *s, int *ntemps, int *swap_every, double *beta)
+{
+    if (!s || !s->ntemps) return 1;
+    if (ntemps) *ntemps = s->ntemps;
+    if (swap_every) *swap_every = s->swap_every;
+    if (beta) memcpy(beta, s->beta.data(), (size_t)s->ntemps * 8);
+    return 0;
+}
+
+extern "C" int mceik_mcmc_temper_stats(mceik_mcmc *s, long long *attempts, long long *accepts, int reset)
+{
+    if (!s || !s->ntemps) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    const size_t n = (size_t)(s->ntemps - 1) * 8;
+    if (attempts && n) HIPCHK(hipMemcpy(attempts, s->d_tcnt, n, hipMemcpyDeviceToHost));
+    if (accepts && n) HIPCHK(hipMemcpy(accepts, s->d_tcnt + s->D.nchains, n, hipMemcpyDeviceToHost));
+    if (reset) HIPCHK(hipMemset(s->d_tcnt, 0, 2 * (size_t)s->D.nchains * 8));
+    return 0;
+}
+
+extern "C" int mceik_mcmc_temper_swap(mceik_mcmc *s, int parity)
+{
+    if (!s || !s->ntemps || (parity != 0 && parity != 1)) return 1;
+    DeviceScope dg(s->device);
+    return temper_round(s, parity);
 }
 
 // After a stream synchronisation: a multi-step launch whose wave gave up

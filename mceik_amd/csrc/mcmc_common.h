@@ -26,6 +26,7 @@ struct McmcDev {
     int *keep_v;                   // [max_samples][keep_stride][nphase][ncell]
     double *keep_logl;             // [max_samples][keep_stride]
     int keep_stride;               // chains per kept slot: the sampler's nchains (a pipe's view covers a part)
+    const double *beta;            // [nchains] inverse temperature per chain (parallel tempering), null: off
 };
 
 // One rank's chain shard as the checkpoint gather sees it (capi.hip

@@ -131,7 +131,10 @@ __device__ __forceinline__ int chain_accept(const McmcDev &D, int c, double ln, 
     const size_t ci = (size_t)c * D.ncm + cell;
     int acc = 0;
     if (ldv(&D.prop_inprior[c])) {
-        acc = ldv(&D.prop_logu[c]) < ln - ldv(&D.logl[c]);
+        // tempered chains sample L^beta: the log ratio scaled by the chain's beta
+        // (one fp64 multiply; the uniform prior is not tempered)
+        const double d = ln - ldv(&D.logl[c]);
+        acc = D.beta ? ldv(&D.prop_logu[c]) < ldv(&D.beta[c]) * d : ldv(&D.prop_logu[c]) < d;
         if (acc) {
             D.logl[c] = ln;
             D.v[ci] = ldv(&D.prop_v[c]);

@@ -24,6 +24,7 @@ struct McmcPostCtx {
     hipStream_t stream;
     const McmcDev *D;
     McmcPost **slot;               // the sampler's posterior pointer (null: off)
+    int ncold;                     // chains the posterior sees: [0, ncold) (parallel tempering: the cold ones)
 };
 int mcmc_post_ctx(mceik_mcmc *s, McmcPostCtx *out);
 
@@ -32,4 +33,5 @@ int mcmc_post_ctx(mceik_mcmc *s, McmcPostCtx *out);
 // on stream st; once every chain of a kept step is queued, count the state.
 hipError_t mcmc_post_accumulate(McmcPost *p, const McmcDev &V, int chain_off, hipStream_t st);
 void mcmc_post_counted(McmcPost *p);
+long long mcmc_post_count(const McmcPost *p);   // states accumulated per chain
 void mcmc_post_free(McmcPost *p);

@@ -186,6 +186,8 @@ void mcmc_post_free(McmcPost *p)
 
 void mcmc_post_counted(McmcPost *p) { p->n++; }
 
+long long mcmc_post_count(const McmcPost *p) { return p->n; }
+
 hipError_t mcmc_post_accumulate(McmcPost *p, const McmcDev &V, int chain_off, hipStream_t st)
 {
     if (V.nchains <= 0) return hipSuccess;
@@ -286,7 +288,9 @@ extern "C" int mceik_mcmc_posterior_accumulate(mceik_mcmc *s)
     McmcPostCtx x;
     if (mcmc_post_ctx(s, &x) || !*x.slot) return 1;
     PostScope dg(x.device);
-    PHIPCHK(mcmc_post_accumulate(*x.slot, *x.D, 0, x.stream));
+    McmcDev V = *x.D;
+    V.nchains = x.ncold;             // tempering: the hot chains' rows stay zero
+    PHIPCHK(mcmc_post_accumulate(*x.slot, V, 0, x.stream));
     mcmc_post_counted(*x.slot);
     return 0;
 }
@@ -332,7 +336,7 @@ extern "C" int mceik_mcmc_posterior_partials(mceik_mcmc *s, mceik_posterior_part
     const int ncm = p->ncm;
     {
         PostScope dg(x.device);
-        hipLaunchKernelGGL(post_reduce_kernel, dim3((ncm + 63) / 64), dim3(64), 0, x.stream, p->P, p->nchains, ncm,
+        hipLaunchKernelGGL(post_reduce_kernel, dim3((ncm + 63) / 64), dim3(64), 0, x.stream, p->P, x.ncold, ncm,
                            p->d_S, p->d_Q, p->d_P);
         PHIPCHK(hipGetLastError());
     }
@@ -350,7 +354,7 @@ extern "C" int mceik_mcmc_posterior_partials(mceik_mcmc *s, mceik_posterior_part
     out->ncm = ncm;
     out->nbins = p->P.nbins;
     out->per_chain = p->P.per_chain;
-    out->nchains = p->nchains;
+    out->nchains = x.ncold;
     out->nkept = p->n;
     return 0;
 }

@@ -324,6 +324,28 @@ def shard(nchains_total, rank, world):
     return lo, lo + base + (1 if rank < extra else 0)
 
 
+def temper_ladder(ntemps, tmax):
+    """The geometric ladder beta[r] = tmax^(-r / (ntemps - 1)), beta[0] = 1
+    exactly (mceik_temper_ladder; host only)."""
+    beta = np.empty(max(int(ntemps), 1), np.float64)
+    if _lib.lib().mceik_temper_ladder(int(ntemps), float(tmax), beta.ctypes.data_as(C.c_void_p)) != 0:
+        raise ValueError("temper_ladder: ntemps >= 1 and a finite tmax >= 1")
+    return beta
+
+
+def cold_chain_ids(nchains_total, world, ntemps):
+    """Global ids of the cold chains (beta = 1) of a tempered run under
+    `shard`'s split: the first nchains / ntemps chains of every rank's shard
+    (replica groups never span ranks).  int64 array, ascending."""
+    out = []
+    for rank in range(world):
+        lo, hi = shard(nchains_total, rank, world)
+        if (hi - lo) % ntemps:
+            raise ValueError(f"rank {rank} holds {hi - lo} chains: not a multiple of ntemps = {ntemps}")
+        out.append(np.arange(lo, lo + (hi - lo) // ntemps, dtype=np.int64))
+    return np.concatenate(out) if out else np.empty(0, np.int64)
+
+
 class Sampler:
     """One GPU's chains (include/mceik.h handle)."""
 
@@ -356,6 +378,8 @@ class Sampler:
         self.max_samples = int(max_samples)
         self._last_full = True          # the last forward solved every model (init / restore)
         self._post = None               # (per_chain, nbins) while the streaming posterior is enabled
+        self._temper = None             # (betas, swap_every) while parallel tempering is enabled
+        self._temper_base = None        # (attempts, accepts) of a restored checkpoint: added to the device counters
 
     @property
     def model_shape(self):
@@ -445,12 +469,22 @@ class Sampler:
               "chain_offset": self.chain_offset, "seed": self.p.seed}
         if self._post is not None:       # the accumulators belong to the state of a run that summarises itself
             ck["posterior"] = self.posterior_raw()
+        if self._temper is not None:     # the ladder decides what the chains sample; the counters ride along
+            att, acc = self.temper_stats()
+            ck["temper"] = {"betas": self._temper[0].copy(), "swap_every": self._temper[1],
+                            "attempts": att, "accepts": acc}
         return ck
 
     def restore(self, ck, recompute_logl=False):
         """Load a checkpoint() dict (mceik_mcmc_restore)."""
         if ck.get("chain_offset", self.chain_offset) != self.chain_offset or ck.get("seed", self.p.seed) != self.p.seed:
             raise ValueError("checkpoint belongs to another chain shard or seed")
+        tk = ck.get("temper")            # a checkpoint without the entry carries no ladder and restores anywhere
+        if tk is not None:
+            mine = self._temper
+            if mine is None or int(tk["swap_every"]) != mine[1] or \
+                    np.asarray(tk["betas"], np.float64).tobytes() != mine[0].tobytes():
+                raise ValueError("the checkpoint was taken with another temperature ladder or swap_every")
         v = np.ascontiguousarray(ck["v"], dtype=np.int32)
         assert v.shape == self.model_shape
         logl = None if recompute_logl else np.ascontiguousarray(ck["logl"], dtype=np.float64)
@@ -464,6 +498,9 @@ class Sampler:
             self._last_full = True
         if "posterior" in ck and self._post is not None:
             self._posterior_set(ck["posterior"])
+        if tk is not None:
+            self.temper_stats(reset=True)
+            self._temper_base = (np.asarray(tk["attempts"], np.int64).copy(), np.asarray(tk["accepts"], np.int64).copy())
 
     # --- streaming posterior (include/mceik.h mceik_mcmc_posterior_*) ---
     def posterior_enable(self, per_chain=True, nbins=64):
@@ -538,6 +575,65 @@ class Sampler:
         out.nchains, out.nkept = int(st.nchains), int(st.nkept)
         return out
 
+    # --- parallel tempering (include/mceik.h mceik_mcmc_temper_*) ---
+    def temper_enable(self, betas=None, ntemps=None, tmax=None, swap_every=1):
+        """Turn replica exchange on: pass the ladder `betas` (betas[0] == 1, non-
+        increasing, > 0) or `ntemps` and `tmax` (the geometric ladder,
+        `temper_ladder`).  nchains must be a multiple of the rungs; rung r of
+        group g is local chain r * G + g, G = nchains / ntemps, so the cold
+        chains are `cold_chains`.  Before every step gs > 0 with gs %
+        swap_every == 0 neighbouring rungs try to swap states (0: never; see
+        `temper_swap`).  Resets the swap counters."""
+        if (betas is None) == (ntemps is None or tmax is None):
+            raise ValueError("temper_enable: pass either betas or ntemps and tmax")
+        b = temper_ladder(ntemps, tmax) if betas is None else np.ascontiguousarray(betas, dtype=np.float64).ravel()
+        o = _lib.TemperOpts(len(b), int(swap_every), b.ctypes.data)
+        rc = self._L.mceik_mcmc_temper_enable(self._h, C.byref(o))
+        if rc != 0:
+            raise (ValueError if rc == 1 else RuntimeError)(
+                f"mceik_mcmc_temper_enable failed ({rc}): nchains % ntemps == 0, betas[0] == 1, 0 < betas[r+1] <= "
+                "betas[r], swap_every >= 0, and no states in an enabled posterior")
+        self._temper = (b.copy(), int(swap_every))
+        self._temper_base = None
+
+    def temper_disable(self):
+        rc = self._L.mceik_mcmc_temper_disable(self._h)
+        if rc != 0:
+            raise (ValueError if rc == 1 else RuntimeError)(f"mceik_mcmc_temper_disable failed ({rc})")
+        self._temper = None
+        self._temper_base = None
+
+    def _temper_on(self):
+        if self._temper is None:
+            raise RuntimeError("tempering is not enabled (Sampler.temper_enable)")
+        return self._temper
+
+    @property
+    def cold_chains(self):
+        """Local indices of the cold chains (beta = 1): range(0, G); every chain while tempering is off."""
+        return range(self.nchains // (len(self._temper[0]) if self._temper is not None else 1))
+
+    def temper_stats(self, reset=False):
+        """(attempts, accepts) int64 [ntemps - 1]: swap rounds per rung pair (r, r + 1)."""
+        n = len(self._temper_on()[0]) - 1
+        att, acc = np.zeros(n, np.int64), np.zeros(n, np.int64)
+        rc = self._L.mceik_mcmc_temper_stats(self._h, att.ctypes.data_as(C.c_void_p), acc.ctypes.data_as(C.c_void_p),
+                                             int(reset))
+        if rc != 0:
+            raise RuntimeError(f"mceik_mcmc_temper_stats failed ({rc})")
+        if self._temper_base is not None:
+            att, acc = att + self._temper_base[0], acc + self._temper_base[1]
+        if reset:
+            self._temper_base = None
+        return att, acc
+
+    def temper_swap(self, parity):
+        """One swap round now (enqueued): rungs r, r + 1 with r % 2 == parity, drawn at the current step."""
+        self._temper_on()
+        rc = self._L.mceik_mcmc_temper_swap(self._h, int(parity))
+        if rc != 0:
+            raise (ValueError if rc == 1 else RuntimeError)(f"mceik_mcmc_temper_swap failed ({rc}): parity 0 or 1")
+
     def fsm_stats(self, reset=False):
         """(FSM kernel ms from hipEvents, launches, executed iterations summed over
         solves, (brick visits, column segments updated, segments changed, wave macro
@@ -556,7 +652,9 @@ class Sampler:
         return n.value
 
     def samples(self, max_states=None, device_ptr=None):
-        """Kept states [k, *model_shape] (host numpy, or copied into device_ptr)."""
+        """Kept states [k, *model_shape] (host numpy, or copied into device_ptr).
+        Every chain is kept; with tempering on, the cold chains are the first
+        G = nchains / ntemps of them (`cold_chains`)."""
         max_states = self.max_samples if max_states is None else max_states
         n = C.c_int(0)
         if device_ptr is not None:
@@ -730,7 +828,9 @@ def gather_kept(smp: Sampler, nchains_total, group=None, dst=0, device=None):
     device tensors -- over RCCL for an nccl group, xGMI on one node -- else as
     host tensors (gloo).  Shards are padded to the largest one, as gather
     needs equal sizes.  Returns (v [nchains_total, ncell] int32, logl
-    [nchains_total] float64) torch tensors on `dst`, (None, None) elsewhere."""
+    [nchains_total] float64) torch tensors on `dst`, (None, None) elsewhere.
+    Every chain is gathered; with tempering on, cold = the first G of each
+    shard (`cold_chain_ids`)."""
     import torch
     import torch.distributed as dist
     rank, world = dist.get_rank(group), dist.get_world_size(group)
@@ -834,7 +934,8 @@ class Comm:
         which 0 = current state, 1 = most recent kept state.  v_out / logl_out:
         torch tensors (device: received in place) or numpy arrays on the root;
         by default the root gets host numpy arrays.  Returns (v, logl) on the
-        root, (None, None) elsewhere."""
+        root, (None, None) elsewhere.  Every chain is gathered; with tempering
+        on, cold = the first G of each shard (`cold_chain_ids`)."""
         is_root = self.rank == root
         if is_root and v_out is None:
             v_out = np.empty((nchains_total,) + smp.model_shape[1:], np.int32)
