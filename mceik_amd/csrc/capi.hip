@@ -129,6 +129,9 @@ static void fill_launch(FsmLaunch &L, const mceik_fsm_batch *b)
     L.max_waves = b->max_waves;
     L.traffic = b->traffic;
     L.step_z = b->step_z;
+    // (fsm16's first-touch instance: one line of u_nan behind every field slot)
+    L.u_stride = L.field_elems +
+                 (fsm_launch_kind(L, is_double) == 16 && fsm16_fixed_layout(L) ? FSM16_UNAN_LINE / 4 : 0);
 }
 
 static int g_device_cus = 0;
@@ -223,7 +226,7 @@ static WsLayout ws_layout(const mceik_fsm_batch *b)
     // fp32 fields are 67 MB, 2048 waves would need 275 GB).  Waves then take
     // several solves each from the queue.
     {
-        const size_t per_wave = 2 * L.field_elems * es + zfw;
+        const size_t per_wave = (L.u_stride + L.field_elems) * es + zfw;
         const long cap = (long)(ws_budget_bytes() / (per_wave ? per_wave : 1));
         if (cap >= 1 && w.nwaves > cap) w.nwaves = (int)cap;
     }
@@ -232,7 +235,7 @@ static WsLayout ws_layout(const mceik_fsm_batch *b)
     size_t slow_bytes = b->slow_mode == 0 ? (size_t)b->nmodel * L.field_elems * es : 0;
     w.u = w.slow + ((slow_bytes + 255) & ~(size_t)255);
     size_t nu = b->u_out ? (size_t)L.nsolve : (size_t)w.nwaves;
-    w.u0 = w.u + nu * L.field_elems * es;
+    w.u0 = w.u + nu * L.u_stride * es;
     w.zf = w.u0 + (size_t)w.nwaves * L.field_elems * es;          // the held stream's z-face copies
     w.total = w.zf + (size_t)w.nwaves * zfw;
     return w;

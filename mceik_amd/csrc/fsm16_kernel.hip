@@ -77,6 +77,7 @@ struct Smem16 {
     unsigned *meta;              // [nr][64] column meta (flags | tz << 9 | cell-cache base << 16)
     unsigned char *fz;           // held stream: per tile, the z-blocks decided in this sweep (sweep z order)
     unsigned *vbits, *cbits;     // held stream: blocks visited / changed in this iteration (bitmaps)
+    unsigned *tbits;             // first touch (fixed instance): blocks written whole in this solve (bitmap)
 };
 template <bool FIXED>
 __device__ __forceinline__ Smem16 smem16_bind(const FsmLaunch &L, unsigned char *base)
@@ -87,7 +88,7 @@ __device__ __forceinline__ Smem16 smem16_bind(const FsmLaunch &L, unsigned char 
         off[3] = F16_LASTPROC; off[4] = F16_LASTCHG; off[2] = F16_ORDER;
         off[9] = F16_ORDER + mceik_align16((size_t)L.ntiles * 2);
         off[10] = off[9] + mceik_align16((size_t)L.ntiles);
-        off[0] = off[10] + f16_bitmap_bytes(L);
+        off[0] = off[10] + f16_bitmap_bytes(L, true);
     } else {
         fsm16_smem_layout(L, off);
     }
@@ -105,6 +106,7 @@ __device__ __forceinline__ Smem16 smem16_bind(const FsmLaunch &L, unsigned char 
     S.fz = base + off[9];
     S.vbits = reinterpret_cast<unsigned *>(base + off[10]);
     S.cbits = S.vbits + (L.nblocks + 31) / 32;
+    S.tbits = S.cbits + (L.nblocks + 31) / 32;           // (FIXED only: the other layouts have no room for it)
     S.scratch = reinterpret_cast<int *>(base + off[6]);
     S.xr = reinterpret_cast<float *>(base + off[7]);
     S.meta = reinterpret_cast<unsigned *>(base + off[8]);
@@ -374,8 +376,31 @@ __device__ __forceinline__ uint32_t halo_offset16(const Fsm16Geo &g, int kb, con
 // of the phase-0 brick at bits 19-31; ring_base holds the position's line
 // base (tile offset + tz << 13).  A step then decodes its brick with a few
 // shifts instead of rederiving zb, validity and the brick flags from tz.
+//
+// First touch (the fixed instance runs without the per-solve u_nan fill, fsm_device.h init_field):
+// a z-block is touched iff all of its 8 KiB in HBM is valid for the current solve; an untouched
+// block is u_nan by definition and its bytes are never loaded.  admit16 sets three more bits of the
+// position word: LW_FIRST, the position is the block's first visit of the solve -- its own lines are
+// loaded from the line of u_nan behind the field instead, and every valid segment of the block is
+// written back, changed or not (W1_FT), which makes it touched; LW_XUN / LW_YUN (edge lanes), the
+// block this lane's x / y halo column comes from was untouched at admission (the face neighbour, or
+// the block itself where the grid ends) -- the halo is loaded from the u_nan line.  A neighbour
+// admitted later in the sweep is downwind: its stores are its own visit's, which this position
+// must not see either way.  The cell-cache base keeps bits 19-28 (< 10 * 32 + 32 + 8).
 #define LW_G(p) (9 + 5 * (p))
 #define LW_CCB 19
+#define LW_XUN (1u << 29)        // (= C_XOWN << 22, C_YOWN << 22: halo_src)
+#define LW_YUN (1u << 30)
+#define LW_FIRST (1u << 31)
+#define W1_FT (1u << 25)         // BInfo16.w1: first touch, store every valid segment
+static_assert((C_XOWN << 22) == LW_XUN && (C_YOWN << 22) == LW_YUN, "halo_src");
+// byte offset of the u_nan line inside the field's buffer resource
+__device__ __forceinline__ uint32_t unan_line(const FsmLaunch &L) { return (uint32_t)L.field_elems * 4u; }
+// a first-touch segment's load address: its half of the u_nan line
+__device__ __forceinline__ uint32_t seg_first(const FsmLaunch &L, uint32_t seg, unsigned w)
+{
+    return (w & LW_FIRST) && seg != OOB ? unan_line(L) + (seg & 64u) : seg;
+}
 template <bool RZ>
 __device__ __forceinline__ unsigned lean_word(const FsmLaunch &L, const Fsm16Geo &g, const ColTile &ct, int tz, int ri,
                                               int u0flag, int zh)
@@ -407,9 +432,12 @@ __device__ __forceinline__ BInfo16 brick_info_lean(const FsmLaunch &L, const Sme
     const unsigned gp = (w >> (ph ? LW_G(1) : LW_G(0))) & 31u;
     const bool pv = pos_valid(p, nstream);
     const bool valid = pv && (gp & 16u);
-    const uint32_t off = base + ((uint32_t)(ph ^ (RZ ? 1 : 0)) << 6);
+    const uint32_t hb = (uint32_t)(ph ^ (RZ ? 1 : 0)) << 6;
+    const uint32_t off = base + hb;
+    const bool ft = (w & LW_FIRST) != 0;
     b.seg = valid ? off : OOB;
-    b.lseg = pv && (w & ((16u << LW_G(0)) | (16u << LW_G(1)))) ? off : OOB;
+    // (first touch: the line is loaded from the u_nan line; seg keeps the true address)
+    b.lseg = pv && (w & ((16u << LW_G(0)) | (16u << LW_G(1)))) ? (ft ? unan_line(L) : base) + hb : OOB;
     b.zh = valid && (gp & 8u) ? off + (RZ ? 8192u - 64u : 124u - 8192u) : OOB;
     // held stream: the z-boundary nodes come from the z-face copies (zf), the run end's z-downwind
     // node of the position's last brick below the column end included
@@ -435,19 +463,25 @@ __device__ __forceinline__ BInfo16 brick_info_lean(const FsmLaunch &L, const Sme
         }
         if (bcm) fl |= F_SLOW;
     }
-    const int ccb = (int)(w >> LW_CCB) + (RZ ? -4 * ph : 4 * ph);
-    b.w1 = (uint32_t)fl | ((uint32_t)ph << 12) | ((uint32_t)p.ri << 20) | (zd ? W1_ZD : 0u);
+    const int ccb = (int)((w >> LW_CCB) & 0x3ffu) + (RZ ? -4 * ph : 4 * ph);
+    b.w1 = (uint32_t)fl | ((uint32_t)ph << 12) | ((uint32_t)p.ri << 20) | (zd ? W1_ZD : 0u) | (ft ? W1_FT : 0u);
     b.w2 = ((uint32_t)ccb & 0xffffu) | ((uint32_t)p.sp << 16);
     b.w3 = ((uint32_t)S.ring_b[p.ri] & 0xffffu) | (bcm << 16);
     return b;
 }
+// (the halo column of an untouched block, LW_XUN / LW_YUN = hbit << 22: the u_nan line)
+__device__ __forceinline__ uint32_t halo_src(const FsmLaunch &L, unsigned me, uint32_t base, unsigned hbit,
+                                             uint32_t hdelta)
+{
+    return (me & (hbit << 22)) ? unan_line(L) : base + ((me & hbit) ? 0u : hdelta);
+}
 template <bool RZ>
-__device__ __forceinline__ uint32_t halo_offset_lean(const Pos &pe, int nstream, int half, unsigned me, uint32_t base,
-                                                     unsigned hbit, uint32_t hdelta)
+__device__ __forceinline__ uint32_t halo_offset_lean(const FsmLaunch &L, const Pos &pe, int nstream, int half,
+                                                     unsigned me, uint32_t base, unsigned hbit, uint32_t hdelta)
 {
     const int ph = pe.zbs;
     const bool valid = pos_valid(pe, nstream) && ((me >> (ph ? LW_G(1) : LW_G(0))) & 16u);
-    const uint32_t o = base + ((me & hbit) ? 0u : hdelta) + ((uint32_t)(ph ^ (RZ ? 1 : 0)) << 6) + (uint32_t)half * 32u;
+    const uint32_t o = halo_src(L, me, base, hbit, hdelta) + ((uint32_t)(ph ^ (RZ ? 1 : 0)) << 6) + (uint32_t)half * 32u;
     return valid ? o : OOB;
 }
 // Whole-line halo loads (the fixed instance): the line base of halo column
@@ -458,11 +492,11 @@ __device__ __forceinline__ uint32_t halo_offset_lean(const Pos &pe, int nstream,
 // first brick staged at the end of the next step, the second one step
 // later), lane r taking quarter r of both halves.
 template <bool RZ>
-__device__ __forceinline__ uint32_t halo_line_lean(const Pos &pe, int nstream, unsigned me, uint32_t base,
-                                                   unsigned hbit, uint32_t hdelta)
+__device__ __forceinline__ uint32_t halo_line_lean(const FsmLaunch &L, const Pos &pe, int nstream, unsigned me,
+                                                   uint32_t base, unsigned hbit, uint32_t hdelta)
 {
     const bool valid = pos_valid(pe, nstream) && (me & ((16u << LW_G(0)) | (16u << LW_G(1))));
-    return valid ? base + ((me & hbit) ? 0u : hdelta) : OOB;
+    return valid ? halo_src(L, me, base, hbit, hdelta) : OOB;
 }
 // lanes r <-> r ^ 2 within each quad (quad_perm 2, 3, 0, 1)
 __device__ __forceinline__ unsigned dpp_swap_quad_half(unsigned v)
@@ -479,10 +513,11 @@ __device__ __forceinline__ BInfo16 brick_info_any(const FsmLaunch &L, const Fsm1
     return brick_info16<RZ>(L, g, kb, S, p, nstream, lx, ly, bc, meta, col);
 }
 template <bool RZ, bool LEAN>
-__device__ __forceinline__ uint32_t halo_offset_any(const Fsm16Geo &g, int kb, const Pos &pe, int nstream, int half,
-                                                    unsigned meta, uint32_t col, unsigned hbit, uint32_t hdelta)
+__device__ __forceinline__ uint32_t halo_offset_any(const FsmLaunch &L, const Fsm16Geo &g, int kb, const Pos &pe,
+                                                    int nstream, int half, unsigned meta, uint32_t col, unsigned hbit,
+                                                    uint32_t hdelta)
 {
-    if (LEAN) return halo_offset_lean<RZ>(pe, nstream, half, meta, col, hbit, hdelta);
+    if (LEAN) return halo_offset_lean<RZ>(L, pe, nstream, half, meta, col, hbit, hdelta);
     return halo_offset16<RZ>(g, kb, pe, nstream, half, meta, col, hbit, hdelta);
 }
 
@@ -521,7 +556,7 @@ __device__ __forceinline__ void admit16(const FsmLaunch &L, const Fsm16Geo &g, c
                                         int entry, int zh, int u0flag, int ri, int C, int lx, int ly, int lxs,
                                         int lys, int rx, int ry, ColTile &ct)
 {
-    unsigned meta = 0;
+    unsigned meta = 0, tw = 0;
     int bid = 0, nbv = 0;
     uint32_t base = 0;
     if (entry >= 0) {
@@ -531,6 +566,18 @@ __device__ __forceinline__ void admit16(const FsmLaunch &L, const Fsm16Geo &g, c
         if ((entry & 0xffffff) != ct.tile) column_tile<float>(L, bc, entry, lx, ly, lxs, lys, rx, ry, ct);
         meta = LEAN ? lean_word<RZ>(L, g, ct, tz, ri, u0flag, zh) : column_word(L, L.kb, ct, tz, ri, u0flag, zh);
         base = (uint32_t)(ty * L.ntx + tx) * tile_bytes<float>(L) + (LEAN ? (uint32_t)tz << 13 : 0u);
+        if (LEAN) {
+            // first touch: the touched bits of the block and of the blocks this lane's x / y halo
+            // columns come from (edge lanes: the face neighbour at the same tz, or the block itself
+            // where the grid ends), read by every lane before lane 0 marks the block
+            const bool xe = (lxs == 0 || lxs == 7) && !(ct.fl & C_XOWN), ye = (lys == 0 || lys == 7) && !(ct.fl & C_YOWN);
+            const int bx = xe ? bid + (((lxs == 0) != (rx != 0)) ? -1 : 1) : bid;
+            const int by = ye ? bid + (((lys == 0) != (ry != 0)) ? -L.ntx : L.ntx) : bid;
+            const unsigned t0 = S.tbits[bid >> 5], t1 = S.tbits[bx >> 5], t2 = S.tbits[by >> 5];
+            tw = t0 | (1u << (bid & 31));
+            meta |= (((t0 >> (bid & 31)) & 1u) ? 0u : LW_FIRST) | (((t1 >> (bx & 31)) & 1u) ? 0u : LW_XUN) |
+                    (((t2 >> (by & 31)) & 1u) ? 0u : LW_YUN);
+        }
     }
     const int nact = L.visit_stats && entry >= 0 ? __builtin_popcountll(__ballot(ct.fl & C_ACT)) : 0;
     asm volatile("" ::: "memory");
@@ -539,6 +586,7 @@ __device__ __forceinline__ void admit16(const FsmLaunch &L, const Fsm16Geo &g, c
         if (entry >= 0) {
             S.lastproc[bid] = (unsigned short)C;
             S.vbits[bid >> 5] |= 1u << (bid & 31);
+            if (LEAN) S.tbits[bid >> 5] = tw;
             if (L.visit_stats) {
                 S.scratch[0] += nbv;
                 S.scratch[1] += nbv * nact;
@@ -745,18 +793,19 @@ __device__ __forceinline__ int sweep16(const FsmLaunch &L, const Fsm16Geo &g, Rs
     // bricks vb (b0) and vb+1 (b1); the loop computes vb+2's (b3) and carries it
     Pos p3, pe;
     pos_init(p3, -d, kb, nr);
-    BInfo16 b0 = brick_info_any<RZ, LEAN>(L, g, kb, S, p3, nstream, lx, ly, bc, S.meta[p3.ri * 64 + lane],
-                                  S.ring_base[p3.ri] + lanecol);
+    // (first touch, LEAN: the prologue's own segments of a first-touch position come from the u_nan line)
+    unsigned mw = S.meta[p3.ri * 64 + lane];
+    BInfo16 b0 = brick_info_any<RZ, LEAN>(L, g, kb, S, p3, nstream, lx, ly, bc, mw, S.ring_base[p3.ri] + lanecol);
     const int pbr = pair_row(0, lane), pbn = pair_row(1, lane);
     {
         float t[16];
-        seg_issue(ur, b0.seg, t);
+        seg_issue(ur, LEAN ? seg_first(L, b0.seg, mw) : b0.seg, t);
         raw_write(S.xr, pbn, t);                      // through this lane's XN row
         load_row16(S.xr, 1, lane, v);
     }
     pos_init(pe, -hd, kb, nr);
     {
-        const uint32_t ho = halo_offset_any<RZ, LEAN>(g, kb, pe, nstream, hh, S.meta[pe.ri * 64 + he],
+        const uint32_t ho = halo_offset_any<RZ, LEAN>(L, g, kb, pe, nstream, hh, S.meta[pe.ri * 64 + he],
                                               S.ring_base[pe.ri] + hcol, hbit, hdelta);
         bload4h(ur, ho, *reinterpret_cast<float (*)[4]>(&hq[0]));
         bload4h(ur, ho + 16u, *reinterpret_cast<float (*)[4]>(&hq[4]));
@@ -766,11 +815,11 @@ __device__ __forceinline__ int sweep16(const FsmLaunch &L, const Fsm16Geo &g, Rs
     TRAF(S, 0, b0.seg != OOB, 64);
     TRAF(S, 2, b0.zh != OOB, 4);
     pos_adv(p3, kb, nr);
-    BInfo16 b1 = brick_info_any<RZ, LEAN>(L, g, kb, S, p3, nstream, lx, ly, bc, S.meta[p3.ri * 64 + lane],
-                                  S.ring_base[p3.ri] + lanecol);
+    mw = S.meta[p3.ri * 64 + lane];
+    BInfo16 b1 = brick_info_any<RZ, LEAN>(L, g, kb, S, p3, nstream, lx, ly, bc, mw, S.ring_base[p3.ri] + lanecol);
     {
         float t[16];
-        seg_issue(ur, b1.seg, t);
+        seg_issue(ur, LEAN ? seg_first(L, b1.seg, mw) : b1.seg, t);
         raw_write(S.xr, pbn, t);                        // brick vb0 + 1: the XN rows
     }
     if (FL) {
@@ -780,8 +829,9 @@ __device__ __forceinline__ int sweep16(const FsmLaunch &L, const Fsm16Geo &g, Rs
         Pos pn = p3;
         pos_adv(pn, kb, nr);
         const bool nl = pn.vb >= 0 && pn.zbs == 1;
-        const uint32_t sn = nl ? brick_info_any<RZ, LEAN>(L, g, kb, S, pn, nstream, lx, ly, bc, S.meta[pn.ri * 64 + lane],
-                                                  S.ring_base[pn.ri] + lanecol).seg
+        mw = S.meta[pn.ri * 64 + lane];
+        const uint32_t sn = nl ? seg_first(L, brick_info_any<RZ, LEAN>(L, g, kb, S, pn, nstream, lx, ly, bc, mw,
+                                                                       S.ring_base[pn.ri] + lanecol).seg, mw)
                                : OOB;
         const bool nlp = dpp_swap_pair((unsigned)nl) != 0u;
         const uint32_t snp = dpp_swap_pair(sn);
@@ -801,7 +851,7 @@ __device__ __forceinline__ int sweep16(const FsmLaunch &L, const Fsm16Geo &g, Rs
         // step 1): the loader of parity 1 starts its line at 1 - hd, the one
         // of parity 0 holds 1 - hd as its second brick.  Both positions are
         // decided (vb <= 1).
-        const uint32_t lo = halo_line_lean<RZ>(pe, nstream, S.meta[pe.ri * 64 + he], S.ring_base[pe.ri] + hcol, hbit,
+        const uint32_t lo = halo_line_lean<RZ>(L, pe, nstream, S.meta[pe.ri * 64 + he], S.ring_base[pe.ri] + hcol, hbit,
                                                hdelta);
         const uint32_t lp = dpp_swap_quad_half(lo);
         const uint32_t l1 = hcme == (hpi ^ 1) ? lo : lp, l0 = hcme == hpi ? lo : lp;
@@ -811,7 +861,7 @@ __device__ __forceinline__ int sweep16(const FsmLaunch &L, const Fsm16Geo &g, Rs
         bload4h(ur, l1 + ob, hB[1]);
         TRAF(S, 1, l1 != OOB, 32);
     } else {
-        const uint32_t ho = halo_offset_any<RZ, LEAN>(g, kb, pe, nstream, hh, S.meta[pe.ri * 64 + he],
+        const uint32_t ho = halo_offset_any<RZ, LEAN>(L, g, kb, pe, nstream, hh, S.meta[pe.ri * 64 + he],
                                               S.ring_base[pe.ri] + hcol, hbit, hdelta);
         bload4h(ur, ho, *reinterpret_cast<float (*)[4]>(&hn[0]));
         bload4h(ur, ho + 16u, *reinterpret_cast<float (*)[4]>(&hn[4]));
@@ -895,7 +945,7 @@ __device__ __forceinline__ int sweep16(const FsmLaunch &L, const Fsm16Geo &g, Rs
             seg_issue(ur, b3.seg, qa);
         zq = __any(b3.zh != OOB) ? bload1(zr_, b3.zh, 0.0f) : 0.0f;
         if (HFL) {
-            const uint32_t lo = halo_line_lean<RZ>(pe, nstream, me, ce, hbit, hdelta);
+            const uint32_t lo = halo_line_lean<RZ>(L, pe, nstream, me, ce, hbit, hdelta);
             const uint32_t lp = dpp_swap_quad_half(lo);
             const uint32_t sl = hcme == (hpi ^ P) ? lo : lp;         // this step's loader column's line
             const uint32_t qo = 16u * (uint32_t)hr;
@@ -907,7 +957,7 @@ __device__ __forceinline__ int sweep16(const FsmLaunch &L, const Fsm16Geo &g, Rs
             TRAF(S, 0, b3.seg != OOB, 64);
             TRAF(S, 2, b3.zh != OOB, 4);
         } else {
-            const uint32_t ho = halo_offset_any<RZ, LEAN>(g, kb, pe, nstream, hh, me, ce, hbit, hdelta);
+            const uint32_t ho = halo_offset_any<RZ, LEAN>(L, g, kb, pe, nstream, hh, me, ce, hbit, hdelta);
             bload4h(ur, ho, *reinterpret_cast<float (*)[4]>(&hnew[0]));
             bload4h(ur, ho + 16u, *reinterpret_cast<float (*)[4]>(&hnew[4]));
             TRAF(S, 1, ho != OOB, 32);
@@ -998,12 +1048,15 @@ __device__ __forceinline__ int sweep16(const FsmLaunch &L, const Fsm16Geo &g, Rs
         // brick back into v and the brick after it into XN
         store_row16(S.xr, 0, lane, v);
         zprev = v[RZ ? 0 : 15];
-        if (__any(changed)) {
+        // (first touch: every valid segment of the block is written, changed or not; the forced
+        // store is neither a change nor a statistic)
+        const bool wr = changed || (LEAN && (b0.w1 & W1_FT));
+        if (__any(wr)) {
             float t[16];
             raw_read(S.xr, pbr, t);
-            raw_store(ur, b0.seg, changed, t);
+            raw_store(ur, b0.seg, wr, t);
         }
-        TRAF(S, 3, changed, 64);
+        TRAF(S, 3, wr && b0.seg != OOB, 64);
         {
             // what this lane changed: the block, its x / y faces (edge columns), its z faces (the
             // block's lowest / highest node of the column)
@@ -1086,6 +1139,32 @@ __device__ __forceinline__ void verify16(const FsmLaunch &L, Rsrc ur, Rsrc u0r, 
             }
         }
     }
+}
+
+// End of a solve (first touch): the z-blocks still untouched -- after an early stop (max_sweeps,
+// maxit, a failed source) or where no front arrived -- are filled with u_nan before the table
+// gather and before the field is handed out.  At convergence in the sampler there are none.
+__device__ __forceinline__ void fill_untouched16(const FsmLaunch &L, Rsrc ur, const Smem16 &S)
+{
+    const int lane = threadIdx.x;
+    float fill[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) fill[i] = Num<float>::unan();
+    asm volatile("" ::: "memory");
+    for (int base = 0; base < L.nblocks; base += 64) {
+        const int k = base + lane;
+        const bool flag = k < L.nblocks && ((S.tbits[k >> 5] >> (k & 31)) & 1u) == 0;
+        unsigned long long m = __ballot(flag);
+        while (m) {
+            const int bid = base + __builtin_ctzll(m);
+            m &= m - 1;
+            const int tz = bid / L.ntiles, id = bid - tz * L.ntiles;
+            fill_block(ur, (uint32_t)id * tile_bytes<float>(L) + ((uint32_t)tz << 13), fill);
+            TRAFU(S, 7, 8192);
+        }
+    }
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
 }
 
 // ---- multi-step sampler launch (L.mc_dev) ----------------------------------
@@ -1251,6 +1330,7 @@ __device__ __forceinline__ void fsm16_body(const FsmLaunch &L)
     const Fsm16Geo g = fsm16_geo(L);
     const int lane = threadIdx.x;
     const uint32_t fbytes = (uint32_t)(L.field_elems * 4);
+    constexpr bool FT = KB16 == 2;                  // first-touch z-blocks instead of the per-solve fill
     build_order16(L, S.order);
     int pass = 0;
     McQueue mq;
@@ -1273,7 +1353,7 @@ __device__ __forceinline__ void fsm16_body(const FsmLaunch &L)
         if (L.solve_clock && lane == 0) L.solve_clock[2 * (size_t)solve] = __builtin_amdgcn_s_memrealtime();
         const int model = (int)solve / L.nstat, station = (int)solve - model * L.nstat;
         const size_t slot = L.slot_per_solve ? solve : blockIdx.x;
-        float *u = reinterpret_cast<float *>(L.u) + slot * L.field_elems;
+        float *u = reinterpret_cast<float *>(L.u) + slot * L.u_stride;
         float *u0 = reinterpret_cast<float *>(L.u0) + (size_t)blockIdx.x * L.field_elems;   // per-wave scratch
         const size_t ncell = (size_t)L.ncx * L.ncy * L.ncz;
         // (a multi-step launch's model phase changes between steps: vector load)
@@ -1288,7 +1368,8 @@ __device__ __forceinline__ void fsm16_body(const FsmLaunch &L)
         }
         const size_t sentry = !L.model_phase ? (size_t)model : (size_t)model * L.nphase + phase;
         const void *slow_model = reinterpret_cast<const float *>(L.slow) + sentry * ncell;
-        const Rsrc ur = make_rsrc(u, fbytes), u0r = make_rsrc(u0, fbytes),
+        // (FT: ur covers the line of u_nan behind the field)
+        const Rsrc ur = make_rsrc(u, fbytes + (FT ? FSM16_UNAN_LINE : 0)), u0r = make_rsrc(u0, fbytes),
                    sr = make_rsrc(slow_model, (uint32_t)(ncell * 4));
         const size_t zfb = zf_bytes(L, 4);
         const Rsrc zfr = make_rsrc(reinterpret_cast<char *>(L.zf) + (size_t)blockIdx.x * zfb, (uint32_t)zfb);
@@ -1300,7 +1381,8 @@ __device__ __forceinline__ void fsm16_body(const FsmLaunch &L)
         unsigned nchg = 0, nsteps = 0;
         BcBoxes bc;
         bc.box = S.box;
-        const bool ok = init_field<float, 1>(L, u, ur, slow_model, L.src + (size_t)station * L.nsrc * 4, bc);
+        const bool ok = init_field<float, 1, FT>(L, u, ur, slow_model, L.src + (size_t)station * L.nsrc * 4, bc,
+                                                 S.tbits);
         // (before the first sweep only the blocks holding boundary-condition nodes are dirty: a block
         // whose nodes and neighbours are all u_nan updates to u_nan; hold_solve_start)
         hold_solve_start(L, hold_lds16(S), bc, g.nr);
@@ -1334,6 +1416,8 @@ __device__ __forceinline__ void fsm16_body(const FsmLaunch &L)
                 }
             }
         }
+        // first touch: the blocks no visit wrote (an early stop, unreachable regions) are u_nan
+        if (FT) fill_untouched16(L, ur, S);
         // ierr: from the last evaluation of node (0,0,0) (the reference's last update)
         int ierr = ierr_last;
         for (int o = 32; o > 0; o >>= 1) ierr = max(ierr, __shfl_xor(ierr, o, 64));
@@ -1355,7 +1439,7 @@ __device__ __forceinline__ void fsm16_body(const FsmLaunch &L)
             if (L.niter) L.niter[solve] = iters;
             if (L.ierr) L.ierr[solve] = ierr;
         }
-        TRAFU(S, 7, (unsigned)(L.field_elems * 4) + (L.ttab ? (unsigned)L.nev * (4u + 64u) : 0u));
+        TRAFU(S, 7, (FT ? 0u : (unsigned)(L.field_elems * 4)) + (L.ttab ? (unsigned)L.nev * (4u + 64u) : 0u));
         TRAF_FLUSH(L, S);
         if (L.ttab) {
             for (int e = lane; e < L.nev; e += 64) L.ttab[(size_t)solve * L.nev + e] = event_time<float>(L, u, e);

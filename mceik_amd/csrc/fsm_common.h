@@ -32,7 +32,9 @@ struct FsmLaunch {
     unsigned magic_rx, magic_ry, magic_rz;   // ceil(2^20 / nr*): cell = (node * magic) >> 20
     int nzq;                     // 128-B line groups per column: ceil(nzb / (16 / es))
     size_t field_elems;          // ntiles * nzq * 64 * (128 / es)
-    void *u;                     // travel-time fields (brick layout, R)
+    size_t u_stride;             // elements between consecutive slots of u: field_elems, plus one 128-B line of
+                                 // u_nan behind every field when the launch runs fsm16's first-touch instance
+    void *u;                     // travel-time fields (brick layout, R), u_stride apart
     void *u0;                    // convergence side field (same layout)
     void *zf;                    // held stream: per-wave copies of every z-block's lowest and highest node per
                                  // column, [nblocks][2][64 columns lx + 8 ly] R (zf_bytes), the values a run
@@ -218,7 +220,8 @@ static inline __host__ __device__ bool fsm16_eligible(const FsmLaunch &L, size_t
 // 5 ring: entry int [nr], block id int [nr], tile base u32 [nr], change mask u32 [nr] | 6 scratch |
 // 7 neighbour rows XR then XN, each [4 quarters][80 rows][4] float | 8 column meta u32 [nr][64] |
 // 9 tile frontier u8 [ntiles] (z-blocks decided in this sweep) | 10 two block bitmaps u32 [nblocks / 32]
-// (visited / changed in this iteration)
+// (visited / changed in this iteration), and in the fixed layout a third: touched in this solve (the
+// first-touch instance, fsm16_kernel.hip)
 #define MCEIK_SMEM16_ARRAYS 11
 // floats per quarter array of the neighbour rows: 80 rows of 4 plus a 16-B pad,
 // so that the x-pair exchange (even lane: quarter 0, odd lane: quarter 1 of the
@@ -238,9 +241,13 @@ static inline __host__ __device__ bool fsm16_fixed_layout(const FsmLaunch &L)
 {
     return fsm16_eligible(L, 4) && L.kb == 4 && L.ccb <= 32 && fsm16_geo(L).nr == F16_NR;
 }
-static inline __host__ __device__ size_t f16_bitmap_bytes(const FsmLaunch &L)
+// The fixed-layout instances skip the per-solve u_nan fill of the field (first-touch z-blocks,
+// fsm16_kernel.hip): every field slot is followed by one 128-B line of u_nan inside its buffer
+// resource, which the loads of blocks not yet written in the solve are redirected to.
+#define FSM16_UNAN_LINE 128
+static inline __host__ __device__ size_t f16_bitmap_bytes(const FsmLaunch &L, bool fixed)
 {
-    return mceik_align16((size_t)((L.nblocks + 31) / 32) * 4 * 2);
+    return mceik_align16((size_t)((L.nblocks + 31) / 32) * 4 * (fixed ? 3 : 2));
 }
 static inline __host__ __device__ size_t fsm16_smem_layout(const FsmLaunch &L, size_t *off)
 {
@@ -250,7 +257,7 @@ static inline __host__ __device__ size_t fsm16_smem_layout(const FsmLaunch &L, s
         off[3] = F16_LASTPROC; off[4] = F16_LASTCHG; off[2] = F16_ORDER;
         off[9] = F16_ORDER + mceik_align16((size_t)L.ntiles * 2);
         off[10] = off[9] + mceik_align16((size_t)L.ntiles);
-        off[0] = off[10] + f16_bitmap_bytes(L);
+        off[0] = off[10] + f16_bitmap_bytes(L, true);
         return off[0] + nbox;
     }
     const Fsm16Geo g = fsm16_geo(L);
@@ -262,7 +269,7 @@ static inline __host__ __device__ size_t fsm16_smem_layout(const FsmLaunch &L, s
     off[3] = o; o += mceik_align16(nb * 2);
     off[4] = o; o += mceik_align16(nb * 2);
     off[9] = o; o += mceik_align16((size_t)L.ntiles);
-    off[10] = o; o += f16_bitmap_bytes(L);
+    off[10] = o; o += f16_bitmap_bytes(L, false);
     off[5] = o; o += mceik_align16(nr * 16);
     off[6] = o; o += MCEIK_SCRATCH_BYTES;
     off[7] = o; o += 2 * 4 * MCEIK_X16Q * 4;

@@ -315,9 +315,23 @@ __device__ __forceinline__ double godunov_v(double a, double b, double c, double
 }
 
 // ---- per-solve setup: u = u_nan, then the source boxes (EIKONAL3D_SETBCS) ----
-template <typename R, int SLOWMODE>
+// FT (fsm16's fixed-layout fp32 instances: a z-block is one 8-KiB line group, tile base + tz << 13):
+// no fill.  A z-block is "touched" (bitmap tbits, LDS) iff all of its 8 KiB is valid for this solve;
+// an untouched block is u_nan by definition and its bytes are never loaded.  Here only the blocks
+// holding a source box's candidate nodes are filled and marked; the sweep writes a block whole at
+// its first visit and the solve's end fills the blocks still untouched.  What is written instead of
+// the field: the line of u_nan behind it (ur covers it), and the half lines past the column's last
+// 16-z brick, which no visit stores.
+template <typename R>
+__device__ __forceinline__ void fill_block(Rsrc ur, uint32_t base, const R (&fill)[8])
+{
+    const uint32_t o = base + (uint32_t)threadIdx.x * 128u;
+#pragma unroll
+    for (int i = 0; i < 128 / (8 * (int)sizeof(R)); i++) bstore8(ur, o + 8u * (uint32_t)sizeof(R) * i, fill);
+}
+template <typename R, int SLOWMODE, bool FT = false>
 __device__ __forceinline__ bool init_field(const FsmLaunch &L, R *u, Rsrc ur, const void *slow_model, const double *src,
-                           BcBoxes &bc)
+                           BcBoxes &bc, unsigned *tbits = nullptr)
 {
     const int lane = threadIdx.x;
     const R UN = Num<R>::unan();
@@ -325,7 +339,22 @@ __device__ __forceinline__ bool init_field(const FsmLaunch &L, R *u, Rsrc ur, co
     R fill[8];
 #pragma unroll
     for (int i = 0; i < 8; i++) fill[i] = UN;
-    for (uint32_t i = lane; i < nvec; i += 64) bstore8(ur, i * 8u * (uint32_t)sizeof(R), fill);
+    if (FT) {
+        for (int w = lane; w < (L.nblocks + 31) / 32; w += 64) tbits[w] = 0;
+        if (lane < 128 / (8 * (int)sizeof(R)))
+            bstore8(ur, (uint32_t)(L.field_elems * sizeof(R)) + (uint32_t)lane * 8u * (uint32_t)sizeof(R), fill);
+        if (mceik_div_up(L.nz, 16) & 1) {
+            for (int t = 0; t < L.ntiles; t++) {
+                const uint32_t o = (uint32_t)t * tile_bytes<R>(L) + ((uint32_t)(L.nzq - 1) << 13) +
+                                   (uint32_t)lane * 128u + 64u;
+                bstore8(ur, o, fill);
+                bstore8(ur, o + 32u, fill);
+            }
+        }
+        asm volatile("" ::: "memory");
+    } else {
+        for (uint32_t i = lane; i < nvec; i += 64) bstore8(ur, i * 8u * (uint32_t)sizeof(R), fill);
+    }
     __builtin_amdgcn_s_waitcnt(0);
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     bc.n = L.nsrc;
@@ -333,7 +362,7 @@ __device__ __forceinline__ bool init_field(const FsmLaunch &L, R *u, Rsrc ur, co
     for (int s = 0; s < L.nsrc; s++) {
         const double *sp = src + (size_t)s * 4;
         const double ts = sp[0];
-        int loc[3][3];
+        int loc[3][3], blo[3] = {0, 0, 0}, bhi[3] = {0, 0, 0};
         const int nn[3] = {L.nx, L.ny, L.nz};
         const double org[3] = {L.x0, L.y0, L.z0};
         for (int a = 0; a < 3; a++) {
@@ -356,8 +385,28 @@ __device__ __forceinline__ bool init_field(const FsmLaunch &L, R *u, Rsrc ur, co
             int lo = 1 << 30, hi = -1;
             for (int i = 0; i < np; i++) { lo = min(lo, loc[a][i] - 1); hi = max(hi, loc[a][i] - 1); }
             if (lane == 0) { bc.box[6 * s + 2 * a] = lo; bc.box[6 * s + 2 * a + 1] = hi; }
+            blo[a] = lo; bhi[a] = hi;
         }
         if (!ok) { bc.n = s; break; }
+        if (FT) {
+            // the (at most 8) blocks of the box, unless an earlier source's box filled them; the
+            // nodes below read and write them (ok: the box lies inside the grid)
+            for (int tz = blo[2] >> 5; tz <= bhi[2] >> 5; tz++)
+                for (int ty = blo[1] >> 3; ty <= bhi[1] >> 3; ty++)
+                    for (int tx = blo[0] >> 3; tx <= bhi[0] >> 3; tx++) {
+                        const int b = (tz * L.nty + ty) * L.ntx + tx;
+                        asm volatile("" ::: "memory");
+                        const unsigned w = tbits[b >> 5];
+                        asm volatile("" ::: "memory");
+                        if (!((w >> (b & 31)) & 1u)) {
+                            fill_block(ur, (uint32_t)(ty * L.ntx + tx) * tile_bytes<R>(L) + ((uint32_t)tz << 13), fill);
+                            if (lane == 0) tbits[b >> 5] = w | (1u << (b & 31));
+                        }
+                    }
+            asm volatile("" ::: "memory");
+            __builtin_amdgcn_s_waitcnt(0);
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        }
         // lanes 0..26 each own one node of the 3x3x3 candidate box
         if (lane < 27) {
             int i = lane % 3, j = (lane / 3) % 3, k = lane / 9;

@@ -1091,7 +1091,7 @@ __global__ __launch_bounds__(64) FSM_WPE void fsm_solve_kernel(FsmLaunch L)
             continue;
         }
         const size_t slot = L.slot_per_solve ? solve : blockIdx.x;
-        R *u = reinterpret_cast<R *>(L.u) + slot * L.field_elems;
+        R *u = reinterpret_cast<R *>(L.u) + slot * L.u_stride;
         R *u0 = reinterpret_cast<R *>(L.u0) + (size_t)blockIdx.x * L.field_elems;   // per-wave scratch
         const void *slow_model;
         uint32_t slow_bytes;
@@ -1253,7 +1253,7 @@ __global__ void from_brick_kernel(const RS *src, RD *dst, FsmLaunch L, int nfiel
         size_t fld = i / nn, e = i - fld * nn;
         int x = (int)(e % L.nx); size_t t = e / L.nx;
         int y = (int)(t % L.ny); int z = (int)(t / L.ny);
-        dst[i] = (RD)src[fld * L.field_elems + brick_index<RS>(L, x, y, z)];
+        dst[i] = (RD)src[fld * L.u_stride + brick_index<RS>(L, x, y, z)];       // (src: the launch's u slots)
     }
 }
 
