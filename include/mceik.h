@@ -270,6 +270,59 @@ int mceik_mcmc_temper_swap(mceik_mcmc *s, int parity);
  * = 1 exactly (ntemps >= 1, finite tmax >= 1, else 1). */
 int mceik_temper_ladder(int ntemps, double tmax, double *beta);
 
+/* ---- multi-cell (block) proposals (csrc/block.hip) --------
+ * Off by default; with it off nothing changes.  A block proposal moves a
+ * smooth neighbourhood of inversion cells of one model at once; the forward
+ * costs the same.  Options: radii rmin, rmax in inversion cells, 0 <= rmin <=
+ * rmax <= 8.
+ *
+ * Draw: the single-cell draw unchanged -- Philox4x32-10, counter {(uint32)step,
+ * (uint32)(step >> 32), 0, 0}, key {global chain, seed}, outputs r0..r3; centre
+ * cell = (r0 * ncm) >> 32 over the chain's [nphase][ncell] entries, phase =
+ * cell / ncell, mag = 1 + ((r1 * dvmax) >> 32), sign = r2 & 1 (1 = minus), U
+ * from r3 -- plus the radius R = rmin + (((uint64)(r2 >> 1) * (rmax - rmin +
+ * 1)) >> 31).
+ *
+ * Footprint: with (cx, cy, cz) the centre within its model (cell % ncell, x
+ * fastest), every offset (dx, dy, dz) in [-R, R]^3 whose target lies inside
+ * [0, ncx) x [0, ncy) x [0, ncz) moves by
+ *   dv = ((int64)mag * w) / (R+1)^3,  w = (R+1-|dx|) (R+1-|dy|) (R+1-|dz|)
+ * (integer floor of non-negative operands; the sign is applied afterwards);
+ * entries with dv == 0 are not touched.  The footprint is clipped at the grid
+ * faces and never leaves the phase's model.  R = 0 is the single-cell
+ * proposal, bit for bit.
+ *
+ * The proposal is inside the prior iff every touched entry's new value is
+ * within its phase's bounds; otherwise it is rejected (the forward still
+ * runs).  The accept rule is unchanged, tempering's beta included; no Hastings
+ * term is needed: the move with the same centre, mag and R and the opposite
+ * sign is drawn with equal probability and its dv are the exact negations.
+ *
+ * While enabled every step is one launch of each kernel (a sampler built for
+ * multi-step launches steps per launch: mceik_mcmc_info.multi_step reports 0
+ * until disable); swap rounds and the streaming posterior run as on the
+ * per-step path.  mceik_mcmc_last's accept flags and mceik_mcmc_last_phase
+ * keep their meaning.  attempts[R] / accepts[R] count the proposals of radius
+ * R and the accepted ones.
+ *
+ * Every function returns 0, 1 on invalid arguments (NULL, radii out of range,
+ * not enabled) or -1 on a device failure. */
+typedef struct mceik_block_opts { int rmin, rmax; } mceik_block_opts;
+/* Turns block proposals on (or replaces the radii); resets the counters.  Synchronises. */
+int mceik_mcmc_block_enable(mceik_mcmc *s, const mceik_block_opts *o);
+/* Later steps are single-cell again; the counters stay until the next enable. */
+int mceik_mcmc_block_disable(mceik_mcmc *s);
+/* The radii in force (either may be NULL). */
+int mceik_mcmc_block_get(mceik_mcmc *s, int *rmin, int *rmax);
+/* attempts, accepts [rmax + 1], by radius (either may be NULL).  Synchronises. */
+int mceik_mcmc_block_stats(mceik_mcmc *s, long long *attempts, long long *accepts, int reset);
+/* Host only: the footprint of one proposal of signed amplitude amp (the
+ * centre's dv, != 0) and radius 0..8 centred on `cell` of an ncx x ncy x ncz
+ * model: the touched cells in x-fastest order of the offsets and their dv
+ * (each up to (2 radius + 1)^3 entries; either may be NULL).  Returns the
+ * touched count, -1 on invalid arguments. */
+int mceik_block_footprint(int ncx, int ncy, int ncz, int cell, int radius, int amp, int *cells, int *dv);
+
 /* ---- multi-rank runs (one process per GPU; csrc/comm.hip) ---------------
  * The sampler's only collective is the checkpoint gather (SURVEY s.8e) over
  * RCCL (xGMI on one node).  Bootstrap as RCCL's: rank 0 calls

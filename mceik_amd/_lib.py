@@ -104,6 +104,11 @@ class TemperOpts(C.Structure):
     _fields_ = [("ntemps", C.c_int), ("swap_every", C.c_int), ("beta", C.c_void_p)]
 
 
+class BlockOpts(C.Structure):
+    """mceik_block_opts (include/mceik.h)."""
+    _fields_ = [("rmin", C.c_int), ("rmax", C.c_int)]
+
+
 # every extern "C" symbol include/*.h declares
 EXPORTS = ("eikonal3d_serial_driver", "eikonal3d_serial_driver_sp", "eikonal3d_batch_solve", "eikonal3d_initialize", "eikonal3d_solve",
            "eikonal3d_finalize", "locate3d_gridsearch__double64", "locate3d_gridsearch__float64",
@@ -122,6 +127,8 @@ EXPORTS = ("eikonal3d_serial_driver", "eikonal3d_serial_driver_sp", "eikonal3d_b
            "mceik_posterior_merge", "mceik_posterior_finish",
            "mceik_mcmc_temper_enable", "mceik_mcmc_temper_disable", "mceik_mcmc_temper_get",
            "mceik_mcmc_temper_stats", "mceik_mcmc_temper_swap", "mceik_temper_ladder",
+           "mceik_mcmc_block_enable", "mceik_mcmc_block_disable", "mceik_mcmc_block_get", "mceik_mcmc_block_stats",
+           "mceik_block_footprint",
            "mceik_parms_defaults", "mceik_parms_set", "mceik_parms_read", "mceik_parms_args", "mceik_parms_write",
            "mceik_comm_available", "mceik_comm_unique_id", "mceik_comm_init", "mceik_comm_finalize", "mceik_mcmc_gather",
            "os_path_exists", "os_path_isdir", "os_path_isfile", "os_makedirs", "os_mkdir")
@@ -241,5 +248,15 @@ def lib():
     L.mceik_mcmc_temper_swap.argtypes = [C.c_void_p, C.c_int]
     L.mceik_temper_ladder.restype = C.c_int
     L.mceik_temper_ladder.argtypes = [C.c_int, C.c_double, C.c_void_p]
+    L.mceik_mcmc_block_enable.restype = C.c_int
+    L.mceik_mcmc_block_enable.argtypes = [C.c_void_p, C.POINTER(BlockOpts)]
+    L.mceik_mcmc_block_disable.restype = C.c_int
+    L.mceik_mcmc_block_disable.argtypes = [C.c_void_p]
+    L.mceik_mcmc_block_get.restype = C.c_int
+    L.mceik_mcmc_block_get.argtypes = [C.c_void_p, pi, pi]
+    L.mceik_mcmc_block_stats.restype = C.c_int
+    L.mceik_mcmc_block_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.mceik_block_footprint.restype = C.c_int
+    L.mceik_block_footprint.argtypes = [C.c_int] * 6 + [C.c_void_p, C.c_void_p]
     _lib = L
     return L

@@ -5,6 +5,7 @@
 // numerics live in fsm_kernel.hip and mcmc_kernels.hip.
 #include <hip/hip_runtime.h>
 #include <float.h>
+#include <limits.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -22,6 +23,7 @@
 #include "rccl_rt.h"
 #include "posterior.h"
 #include "temper.h"
+#include "block.h"
 
 hipError_t fsm_launch(const FsmLaunch &L, int is_double, int nwaves, hipStream_t st);
 hipError_t fsm_zero_words(unsigned *p, int n, hipStream_t st);
@@ -1561,6 +1563,12 @@ struct mceik_mcmc {
     double *d_beta;                    // [nchains] the chains' beta (D.beta while ntemps > 1)
     int *d_tflag;                      // [nchains] the round's swap flag per pair
     unsigned long long *d_tcnt;        // [2][nchains] attempts, accepts per rung pair
+    // Block proposals (block.hip); off by default.  B holds the
+    // cell grid from init on; while on, every step takes the per-step branch
+    // with block.hip's two kernels in place of propose / accept.
+    bool block_on;
+    BlockDev B, pB[MCEIK_MAX_PIPES];
+    unsigned long long *d_bcnt;        // [2][MCEIK_BLOCK_RMAX + 1] attempts, accepts by radius
     hipStream_t stream;
     void *ws;
     size_t ws_bytes;
@@ -1719,6 +1727,15 @@ static McmcDev dev_view(const McmcDev &D, int off, int n)
     if (V.keep_v) V.keep_v += oc;
     if (V.keep_logl) V.keep_logl += o;
     if (V.beta) V.beta += o;
+    return V;
+}
+
+// The same view of the block state's per-chain arrays (the counters are the sampler's).
+static BlockDev dev_view(const BlockDev &B, int off)
+{
+    BlockDev V = B;
+    if (V.prop_amp) V.prop_amp += off;
+    if (V.prop_rad) V.prop_rad += off;
     return V;
 }
 
@@ -1931,6 +1948,8 @@ extern "C" int mceik_mcmc_init(const struct mceik_parms_struct *parms, const str
     D.keep_stride = nch;
     D.vmin = o->vmin; D.vmax = o->vmax; D.dvmax = o->dvmax; D.seed = o->seed;
     D.vsmin = nphase == 2 ? o->vsmin : 0; D.vsmax = nphase == 2 ? o->vsmax : 0;
+    memset(&s->B, 0, sizeof(s->B));
+    s->B.ncx = ncx; s->B.ncy = ncy; s->B.ncz = ncz;
     // host-side problem tables
     std::vector<double> src((size_t)nstat * 4);
     for (int i = 0; i < nstat; i++) {
@@ -2176,7 +2195,9 @@ static int temper_round(mceik_mcmc *s, int parity)
 // kernel this call queued on the internal streams.
 static int mcmc_steps(mceik_mcmc *s, int nsteps)
 {
-    if (s->persist) {
+    // block proposals: the multi-step kernel's epilogue is single-cell, so a
+    // sampler built for multi-step launches (one pipe) steps per launch
+    if (s->persist && !s->block_on) {
         // the first step's proposals here, then up to MCEIK_MC_CHUNK steps per
         // FSM launch (the kernel accepts, keeps and proposes the rest)
         for (int done = 0; done < nsteps;) {
@@ -2206,6 +2227,7 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
         return 0;
     }
     const int np = s->npipe;
+    const bool blk = s->block_on;
     for (int i = 0; i < nsteps; i++) {
         uint64_t step = (uint64_t)s->step;
         int slot = -1;
@@ -2229,16 +2251,18 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
         }
         if (np > 1) {
             for (int k = 0; k < np; k++) {
-                HIPCHK(mcmc_propose(s->pD[k], step, s->pst[k]));
+                HIPCHK(blk ? block_propose(s->pD[k], s->pB[k], step, s->pst[k])
+                           : mcmc_propose(s->pD[k], step, s->pst[k]));
                 if (mcmc_forward(s, true, k)) return -1;
-                HIPCHK(mcmc_accept(s->pD[k], slot, s->pst[k]));
+                HIPCHK(blk ? block_accept(s->pD[k], s->pB[k], slot, s->pst[k])
+                           : mcmc_accept(s->pD[k], slot, s->pst[k]));
                 if (post)           // the pipe's rows of the accumulators, offset like its keep_v (dev_view)
                     HIPCHK(post_add(s, s->pD[k], s->pD[k].chain_offset - s->D.chain_offset, s->pst[k]));
             }
         } else {
-            HIPCHK(mcmc_propose(s->D, step, s->stream));
+            HIPCHK(blk ? block_propose(s->D, s->B, step, s->stream) : mcmc_propose(s->D, step, s->stream));
             if (mcmc_forward(s, true)) return -1;
-            HIPCHK(mcmc_accept(s->D, slot, s->stream));
+            HIPCHK(blk ? block_accept(s->D, s->B, slot, s->stream) : mcmc_accept(s->D, slot, s->stream));
             if (post) HIPCHK(post_add(s, s->D, 0, s->stream));
         }
         if (post) mcmc_post_counted(s->post);
@@ -2362,6 +2386,81 @@ extern "C" int mceik_mcmc_temper_swap(mceik_mcmc *s, int parity)
     if (!s || !s->ntemps || (parity != 0 && parity != 1)) return 1;
     DeviceScope dg(s->device);
     return temper_round(s, parity);
+}
+
+// ---------------------------------------------------------------------------
+// block proposals (include/mceik.h mceik_mcmc_block_*)
+
+extern "C" int mceik_mcmc_block_enable(mceik_mcmc *s, const mceik_block_opts *o)
+{
+    if (!s || !o || o->rmin < 0 || o->rmax < o->rmin || o->rmax > MCEIK_BLOCK_RMAX) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    const int nch = s->D.nchains, nr = MCEIK_BLOCK_RMAX + 1;
+    if (!s->d_bcnt) {                  // all three or none: a failed enable leaves the sampler as it was
+        unsigned long long *cnt = nullptr;
+        int *amp = nullptr, *rad = nullptr;
+        if (dalloc(s, &cnt, 2 * (size_t)nr) || dalloc(s, &amp, nch) || dalloc(s, &rad, nch)) return -1;
+        s->d_bcnt = cnt;
+        s->B.prop_amp = amp;
+        s->B.prop_rad = rad;
+    }
+    HIPCHK(hipMemset(s->d_bcnt, 0, 2 * (size_t)nr * 8));
+    s->B.rmin = o->rmin;
+    s->B.rmax = o->rmax;
+    s->B.attempts = s->d_bcnt;
+    s->B.accepts = s->d_bcnt + nr;
+    for (int k = 0; k < s->npipe && s->npipe > 1; k++)
+        s->pB[k] = dev_view(s->B, s->pD[k].chain_offset - s->D.chain_offset);
+    s->block_on = true;
+    return 0;
+}
+
+extern "C" int mceik_mcmc_block_disable(mceik_mcmc *s)
+{
+    if (!s) return 1;
+    s->block_on = false;               // host state only: queued steps keep the kernels they were queued with
+    return 0;
+}
+
+extern "C" int mceik_mcmc_block_get(mceik_mcmc *s, int *rmin, int *rmax)
+{
+    if (!s || !s->block_on) return 1;
+    if (rmin) *rmin = s->B.rmin;
+    if (rmax) *rmax = s->B.rmax;
+    return 0;
+}
+
+extern "C" int mceik_mcmc_block_stats(mceik_mcmc *s, long long *attempts, long long *accepts, int reset)
+{
+    if (!s || !s->block_on) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    const int nr = MCEIK_BLOCK_RMAX + 1;
+    const size_t n = (size_t)(s->B.rmax + 1) * 8;
+    if (attempts) HIPCHK(hipMemcpy(attempts, s->B.attempts, n, hipMemcpyDeviceToHost));
+    if (accepts) HIPCHK(hipMemcpy(accepts, s->B.accepts, n, hipMemcpyDeviceToHost));
+    if (reset) HIPCHK(hipMemset(s->d_bcnt, 0, 2 * (size_t)nr * 8));
+    return 0;
+}
+
+extern "C" int mceik_block_footprint(int ncx, int ncy, int ncz, int cell, int radius, int amp, int *cells, int *dv)
+{
+    if (ncx < 1 || ncy < 1 || ncz < 1 || (long long)ncx * ncy * ncz > INT_MAX || cell < 0 || cell >= ncx * ncy * ncz ||
+        radius < 0 || radius > MCEIK_BLOCK_RMAX || amp == 0 || amp == INT_MIN)
+        return -1;
+    const int cx = cell % ncx, cy = (cell / ncx) % ncy, cz = cell / (ncx * ncy);
+    const int mag = amp < 0 ? -amp : amp, n = 2 * radius + 1;
+    int cnt = 0;
+    for (int k = 0; k < n * n * n; k++) {
+        int t = 0;
+        const int d = block_dv(ncx, ncy, ncz, cx, cy, cz, radius, mag, k, &t);
+        if (!d) continue;
+        if (cells) cells[cnt] = t;
+        if (dv) dv[cnt] = amp < 0 ? -d : d;
+        cnt++;
+    }
+    return cnt;
 }
 
 // After a stream synchronisation: a multi-step launch whose wave gave up
@@ -2531,7 +2630,7 @@ extern "C" int mceik_mcmc_get_info(mceik_mcmc *s, mceik_mcmc_info *info)
     DeviceScope dg(s->device);
     memset(info, 0, sizeof(*info));
     info->npipe = s->npipe;
-    info->multi_step = s->persist ? 1 : 0;
+    info->multi_step = s->persist && !s->block_on ? 1 : 0;   // block proposals step per launch
     info->nphase = s->D.nphase;
     info->masked_s = s->masked_s;
     FsmLaunch L;

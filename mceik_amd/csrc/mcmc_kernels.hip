@@ -326,6 +326,13 @@ hipError_t mcmc_accept(const McmcDev &D, int keep_slot, hipStream_t st)
     return hipGetLastError();
 }
 
+// The kept-state copy alone (block.hip's accept launches it after its own kernel).
+hipError_t mcmc_keep(const McmcDev &D, int keep_slot, hipStream_t st)
+{
+    hipLaunchKernelGGL(keep_kernel, dim3(512), dim3(256), 0, st, D, keep_slot);
+    return hipGetLastError();
+}
+
 hipError_t l2_gridsearch(int ldgrd, int ngrd, int nuse, int iwantOT, double t0use, const int *use,
                          const double *tc, const double *wt, double xnorm, const double *test,
                          double *t0, double *objfn, hipStream_t st)

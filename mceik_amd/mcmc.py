@@ -346,6 +346,20 @@ def cold_chain_ids(nchains_total, world, ntemps):
     return np.concatenate(out) if out else np.empty(0, np.int64)
 
 
+def block_footprint(p, cell, radius, amp):
+    """The footprint of one block proposal (mceik_block_footprint; host only):
+    (cells, dv) int32 arrays -- the cells of one ncx x ncy x ncz model of
+    `p` that a proposal of signed amplitude `amp` and radius `radius` centred
+    on `cell` touches, in x-fastest order of the offsets, and what each moves by."""
+    n = (2 * int(radius) + 1) ** 3 if 0 <= int(radius) <= 8 else 1
+    cells, dv = np.empty(n, np.int32), np.empty(n, np.int32)
+    cnt = _lib.lib().mceik_block_footprint(int(p.ncx), int(p.ncy), int(p.ncz), int(cell), int(radius), int(amp),
+                                           cells.ctypes.data_as(C.c_void_p), dv.ctypes.data_as(C.c_void_p))
+    if cnt < 0:
+        raise ValueError("block_footprint: cell inside the model, radius in [0, 8], amp != 0")
+    return cells[:cnt].copy(), dv[:cnt].copy()
+
+
 class Sampler:
     """One GPU's chains (include/mceik.h handle)."""
 
@@ -380,6 +394,8 @@ class Sampler:
         self._post = None               # (per_chain, nbins) while the streaming posterior is enabled
         self._temper = None             # (betas, swap_every) while parallel tempering is enabled
         self._temper_base = None        # (attempts, accepts) of a restored checkpoint: added to the device counters
+        self._block = None              # (rmin, rmax) while block proposals are enabled
+        self._block_base = None         # (attempts, accepts) of a restored checkpoint, as _temper_base
 
     @property
     def model_shape(self):
@@ -473,6 +489,9 @@ class Sampler:
             att, acc = self.temper_stats()
             ck["temper"] = {"betas": self._temper[0].copy(), "swap_every": self._temper[1],
                             "attempts": att, "accepts": acc}
+        if self._block is not None:      # the radii decide what the chains propose; the counters ride along
+            att, acc = self.block_stats()
+            ck["block"] = {"rmin": self._block[0], "rmax": self._block[1], "attempts": att, "accepts": acc}
         return ck
 
     def restore(self, ck, recompute_logl=False):
@@ -485,6 +504,9 @@ class Sampler:
             if mine is None or int(tk["swap_every"]) != mine[1] or \
                     np.asarray(tk["betas"], np.float64).tobytes() != mine[0].tobytes():
                 raise ValueError("the checkpoint was taken with another temperature ladder or swap_every")
+        bk = ck.get("block")             # likewise: a checkpoint without the entry restores anywhere
+        if bk is not None and (self._block is None or (int(bk["rmin"]), int(bk["rmax"])) != self._block):
+            raise ValueError("the checkpoint was taken with other block-proposal radii")
         v = np.ascontiguousarray(ck["v"], dtype=np.int32)
         assert v.shape == self.model_shape
         logl = None if recompute_logl else np.ascontiguousarray(ck["logl"], dtype=np.float64)
@@ -501,6 +523,9 @@ class Sampler:
         if tk is not None:
             self.temper_stats(reset=True)
             self._temper_base = (np.asarray(tk["attempts"], np.int64).copy(), np.asarray(tk["accepts"], np.int64).copy())
+        if bk is not None:
+            self.block_stats(reset=True)
+            self._block_base = (np.asarray(bk["attempts"], np.int64).copy(), np.asarray(bk["accepts"], np.int64).copy())
 
     # --- streaming posterior (include/mceik.h mceik_mcmc_posterior_*) ---
     def posterior_enable(self, per_chain=True, nbins=64):
@@ -633,6 +658,44 @@ class Sampler:
         rc = self._L.mceik_mcmc_temper_swap(self._h, int(parity))
         if rc != 0:
             raise (ValueError if rc == 1 else RuntimeError)(f"mceik_mcmc_temper_swap failed ({rc}): parity 0 or 1")
+
+    # --- block proposals (include/mceik.h mceik_mcmc_block_*) ---
+    def block_enable(self, rmin=0, rmax=2):
+        """Turn multi-cell proposals on: every step draws a radius R in [rmin,
+        rmax] (inversion cells, 0 <= rmin <= rmax <= 8) beside the single-cell
+        draw and moves the cells within R of the centre by the magnitude
+        scaled with a separable triangular weight (`block_footprint`).  R = 0
+        is the single-cell proposal.  Every step is then one launch (`info()
+        ["multi_step"]` is False until `block_disable`).  Resets the counters."""
+        o = _lib.BlockOpts(int(rmin), int(rmax))
+        rc = self._L.mceik_mcmc_block_enable(self._h, C.byref(o))
+        if rc != 0:
+            raise (ValueError if rc == 1 else RuntimeError)(
+                f"mceik_mcmc_block_enable failed ({rc}): 0 <= rmin <= rmax <= 8")
+        self._block = (int(rmin), int(rmax))
+        self._block_base = None
+
+    def block_disable(self):
+        if self._L.mceik_mcmc_block_disable(self._h) != 0:
+            raise RuntimeError("mceik_mcmc_block_disable failed")
+        self._block = None
+        self._block_base = None
+
+    def block_stats(self, reset=False):
+        """(attempts, accepts) int64 [rmax + 1]: proposals and accepted proposals by radius."""
+        if self._block is None:
+            raise RuntimeError("block proposals are not enabled (Sampler.block_enable)")
+        n = self._block[1] + 1
+        att, acc = np.zeros(n, np.int64), np.zeros(n, np.int64)
+        rc = self._L.mceik_mcmc_block_stats(self._h, att.ctypes.data_as(C.c_void_p), acc.ctypes.data_as(C.c_void_p),
+                                            int(reset))
+        if rc != 0:
+            raise RuntimeError(f"mceik_mcmc_block_stats failed ({rc})")
+        if self._block_base is not None:
+            att, acc = att + self._block_base[0], acc + self._block_base[1]
+        if reset:
+            self._block_base = None
+        return att, acc
 
     def fsm_stats(self, reset=False):
         """(FSM kernel ms from hipEvents, launches, executed iterations summed over
