@@ -13,8 +13,7 @@
 #include "block.h"
 #include "mcmc_common.h"
 #include "mcmc_device.h"
-
-hipError_t mcmc_keep(const McmcDev &D, int keep_slot, hipStream_t st);      // mcmc_kernels.hip
+#include "mcmc_host.h"
 
 #define BLOCK_THREADS 256
 #define BLOCK_CHAINS (BLOCK_THREADS / 64)

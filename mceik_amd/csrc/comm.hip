@@ -21,22 +21,9 @@
 #include <vector>
 
 #include "../../include/mceik.h"
+#include "host_util.h"
 #include "rccl_rt.h"
 #include "mcmc_common.h"
-
-// Runs the calling scope on `dev` and restores the caller's device.
-struct DevScope {
-    int prev = -1;
-    explicit DevScope(int dev)
-    {
-        if (hipGetDevice(&prev) == hipSuccess && prev != dev) hipSetDevice(dev);
-        else prev = -1;
-    }
-    ~DevScope()
-    {
-        if (prev >= 0) hipSetDevice(prev);
-    }
-};
 
 // true if p is device memory of GPU `dev` (the gather then receives into it)
 static bool on_device(const void *p, int dev)
@@ -65,14 +52,6 @@ struct mceik_comm {
             return -1;                                                                     \
         }                                                                                  \
     } while (0)
-#define HIPCHK2(x)                                                                         \
-    do {                                                                                   \
-        hipError_t e_ = (x);                                                               \
-        if (e_ != hipSuccess) {                                                            \
-            fprintf(stderr, "mceik_comm: %s failed: %s\n", #x, hipGetErrorString(e_));     \
-            return -1;                                                                     \
-        }                                                                                  \
-    } while (0)
 
 extern "C" int mceik_comm_available(void)
 {
@@ -94,7 +73,7 @@ extern "C" int mceik_comm_init(const unsigned char id[MCEIK_COMM_ID_BYTES], int 
 {
     if (!id || !out || nranks < 1 || rank < 0 || rank >= nranks || !mceik_rccl().ok) return 1;
     *out = nullptr;
-    DevScope dg(device);
+    DeviceScope dg(device);
     mceik_comm *c = new mceik_comm();
     c->nranks = nranks; c->rank = rank; c->device = device;
     ncclUniqueId u;
@@ -121,7 +100,7 @@ extern "C" int mceik_comm_finalize(mceik_comm **pc)
     mceik_comm *c = *pc;
     ncclResult_t r;
     {
-        DevScope dg(c->device);
+        DeviceScope dg(c->device);
         hipStreamSynchronize(c->stream);
         r = mceik_rccl().CommDestroy(c->comm);
         hipStreamDestroy(c->stream);
@@ -145,7 +124,7 @@ extern "C" int mceik_mcmc_gather(mceik_mcmc *s, mceik_comm *c, int which, int nc
                                  int *v_out, double *logl_out)
 {
     if (!s || !c || root < 0 || root >= c->nranks || nchains_total < 1) return 1;
-    DevScope dg(c->device);
+    DeviceScope dg(c->device);
     McmcShard sh;
     const int view = mcmc_shard_view(s, which, &sh);
     const int have = view == 0;

@@ -27,6 +27,7 @@
 #include "fsm_common.h"
 #include "fsm_device.h"
 #include "fsm_hold.h"
+#include "fsm_host.h"
 #include "fsm_update.h"
 #include "mcmc_device.h"
 

@@ -24,6 +24,7 @@
 #include "fsm_common.h"
 #include "fsm_device.h"
 #include "fsm_hold.h"
+#include "fsm_host.h"
 #include "fsm_update.h"
 
 // The compact-layout fp64 instances run the held z-block stream (fsm_hold.h),
@@ -1259,7 +1260,7 @@ __global__ void from_brick_kernel(const RS *src, RD *dst, FsmLaunch L, int nfiel
 
 }  // namespace
 
-// ---- host-side launchers (C++ linkage, used by capi.hip) ---------------------
+// ---- host-side launchers (C++ linkage, fsm_host.h; used by fsm_batch.hip) ---------------------
 template <typename R, int SLOWMODE, bool FAST, int ZSH, int CCR, int KB>
 static hipError_t launch_fsm(const FsmLaunch &L, int nwaves, hipStream_t st)
 {
@@ -1309,8 +1310,6 @@ static int variant(const FsmLaunch &L, int is_double)
 // the 16-z-step kernel (fsm16_kernel.hip) serves the fp32 cell-cache
 // instances (variants 7, 8) when fsm16_eligible(); MCEIK_FSM16=0 keeps the
 // 8-z kernel (A/B measurements)
-hipError_t fsm16_launch(const FsmLaunch &L, int nwaves, hipStream_t st);
-int fsm16_occupancy(const FsmLaunch &L);
 static bool use_fsm16(const FsmLaunch &L, int is_double)
 {
     static const bool on = [] { const char *e = getenv("MCEIK_FSM16"); return !(e && e[0] == '0'); }();

@@ -362,7 +362,7 @@ __global__ void single_pad_kernel(const RS *src, RD *dst, int nx, int ny, int nz
 // nodes of a level are independent), so the result is bitwise the reference's
 // run with one MPI rank per block.  fp64, the padded layout of SingleLaunch.
 //
-// Across ranks (one block per rank, blocks_solve_ranks in capi.hip) a rank
+// Across ranks (one block per rank, blocks_solve_ranks in dropin.hip) a rank
 // sweeps block b0 alone on a grid whose other nodes change only in the halo
 // swap between sweeps, so snap is u itself.  ierr: the reference's EVAL_UPDATE3D
 // ierr of the last level, the corner node of the rank's local grid (its block

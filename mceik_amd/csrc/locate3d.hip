@@ -1,6 +1,6 @@
 // locate3d.hip -- the reference's MPI location driver entry points
 // (include/locate.h; reference locate.f90:322-689, include/locate.h:10-23),
-// host code over the batched GPU relocation (capi.hip mceik_relocate).
+// host code over the batched GPU relocation (locate_dropin.hip mceik_relocate).
 //
 // locate3d_initialize follows LOCATE3D_INITIALIZE (locate.f90:562-677): the
 // master reads the model dimensions from the travel-time file and broadcasts
@@ -31,8 +31,6 @@
 #include "../../include/mceik_eikonal.h"
 #include "../../include/mpiutils.h"
 #include "mpi_rt.h"
-
-extern "C" MCEIK_HIDDEN int mceik_mpiutils_initialized(void);
 
 namespace {
 

@@ -29,7 +29,7 @@ struct McmcDev {
     const double *beta;            // [nchains] inverse temperature per chain (parallel tempering), null: off
 };
 
-// One rank's chain shard as the checkpoint gather sees it (capi.hip
+// One rank's chain shard as the checkpoint gather sees it (sampler_api.hip
 // mcmc_shard_view -> comm.hip).  stream is a hipStream_t.
 struct mceik_mcmc;
 struct McmcShard {

@@ -6,8 +6,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gridsearch.h"
 #include "mcmc_common.h"
 #include "mcmc_device.h"
+#include "mcmc_host.h"
 
 namespace {
 

@@ -20,6 +20,11 @@ MCEIK_HIDDEN int mceik_mpi_barrier(int fcomm);
 MCEIK_HIDDEN int mceik_mpi_comm_dup(int fcomm, int *fout);
 MCEIK_HIDDEN int mceik_mpi_comm_split(int fcomm, int color, int key, int *fout);
 MCEIK_HIDDEN int mceik_mpi_comm_free(int fcomm);
+/* nmsg messages: dir[k] = 0 sends count[k] doubles to peer[k], 1 receives; all complete on return */
+MCEIK_HIDDEN int mceik_mpi_exchange_double(int fcomm, int nmsg, const int *dir, const int *peer, const int *tag,
+                                           double *const *buf, const int *count);
+/* mpiutils.c: mpiutils_initialize3d has split the communicators */
+MCEIK_HIDDEN int mceik_mpiutils_initialized(void);
 #ifdef __cplusplus
 }
 #endif

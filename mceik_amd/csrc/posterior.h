@@ -18,7 +18,7 @@ struct PostDev {
 
 struct McmcPost;                   // a sampler's posterior state (posterior.hip)
 
-// What posterior.hip needs of a sampler (capi.hip fills it).
+// What posterior.hip needs of a sampler (sampler_api.hip fills it).
 struct McmcPostCtx {
     int device;
     hipStream_t stream;
@@ -28,7 +28,7 @@ struct McmcPostCtx {
 };
 int mcmc_post_ctx(mceik_mcmc *s, McmcPostCtx *out);
 
-// The step loop's side (capi.hip mcmc_steps): add the current models of the
+// The step loop's side (sampler.hip mcmc_steps): add the current models of the
 // chains in view V (chains [chain_off, chain_off + V.nchains) of the sampler)
 // on stream st; once every chain of a kept step is queued, count the state.
 hipError_t mcmc_post_accumulate(McmcPost *p, const McmcDev &V, int chain_off, hipStream_t st);

@@ -16,20 +16,12 @@
 #include <vector>
 
 #include "../../include/mceik.h"
+#define HIPCHK_WHO "mceik_posterior"
+#include "host_util.h"
 #include "posterior.h"
 
 #define POST_TILE 64               // model entries per block: lane = entry
 #define POST_SLICE 64              // chains per block: wave w takes chains w, w + 4, ... of the slice
-
-#define PHIPCHK(x)                                                                     \
-    do {                                                                               \
-        hipError_t e_ = (x);                                                           \
-        if (e_ != hipSuccess) {                                                        \
-            fprintf(stderr, "mceik_posterior: %s failed: %s (%s:%d)\n", #x,            \
-                    hipGetErrorString(e_), __FILE__, __LINE__);                        \
-            return -1;                                                                 \
-        }                                                                              \
-    } while (0)
 
 // Histogram bin of value v in [lo, lo + span): (v - lo) * nbins / span in
 // integers, clamped to [0, nbins - 1].  narrow: span * nbins fits 31 bits, so
@@ -206,27 +198,12 @@ hipError_t mcmc_post_accumulate(McmcPost *p, const McmcDev &V, int chain_off, hi
     return hipGetLastError();
 }
 
-namespace {
-struct PostScope {                 // run on the sampler's device, restore the caller's
-    int prev = -1;
-    explicit PostScope(int dev)
-    {
-        if (hipGetDevice(&prev) == hipSuccess && prev != dev) hipSetDevice(dev);
-        else prev = -1;
-    }
-    ~PostScope()
-    {
-        if (prev >= 0) hipSetDevice(prev);
-    }
-};
-}  // namespace
-
 static int post_zero(McmcPost *p, hipStream_t st)
 {
     const size_t n = post_rows(p) * p->ncm;
-    PHIPCHK(hipMemsetAsync(p->P.sum, 0, n * 8, st));
-    PHIPCHK(hipMemsetAsync(p->P.sumsq, 0, n * 8, st));
-    if (p->P.hist) PHIPCHK(hipMemsetAsync(p->P.hist, 0, (size_t)p->ncm * p->P.nbins * 4, st));
+    HIPCHK(hipMemsetAsync(p->P.sum, 0, n * 8, st));
+    HIPCHK(hipMemsetAsync(p->P.sumsq, 0, n * 8, st));
+    if (p->P.hist) HIPCHK(hipMemsetAsync(p->P.hist, 0, (size_t)p->ncm * p->P.nbins * 4, st));
     p->n = 0;
     return 0;
 }
@@ -236,11 +213,11 @@ extern "C" int mceik_mcmc_posterior_enable(mceik_mcmc *s, const mceik_posterior_
     McmcPostCtx x;
     if (!o || mcmc_post_ctx(s, &x)) return 1;
     if (o->nbins < 0 || o->nbins > MCEIK_POST_MAX_BINS) return 1;
-    PostScope dg(x.device);
+    DeviceScope dg(x.device);
     const int per_chain = o->per_chain ? 1 : 0;
     McmcPost *p = *x.slot;
     if (p && (p->P.per_chain != per_chain || p->P.nbins != o->nbins)) {
-        PHIPCHK(hipStreamSynchronize(x.stream));
+        HIPCHK(hipStreamSynchronize(x.stream));
         mcmc_post_free(p);
         *x.slot = p = nullptr;
     }
@@ -276,7 +253,7 @@ extern "C" int mceik_mcmc_posterior_disable(mceik_mcmc *s)
     McmcPostCtx x;
     if (mcmc_post_ctx(s, &x)) return 1;
     if (!*x.slot) return 0;
-    PostScope dg(x.device);
+    DeviceScope dg(x.device);
     const hipError_t e = hipStreamSynchronize(x.stream);
     mcmc_post_free(*x.slot);
     *x.slot = nullptr;
@@ -287,10 +264,10 @@ extern "C" int mceik_mcmc_posterior_accumulate(mceik_mcmc *s)
 {
     McmcPostCtx x;
     if (mcmc_post_ctx(s, &x) || !*x.slot) return 1;
-    PostScope dg(x.device);
+    DeviceScope dg(x.device);
     McmcDev V = *x.D;
     V.nchains = x.ncold;             // tempering: the hot chains' rows stay zero
-    PHIPCHK(mcmc_post_accumulate(*x.slot, V, 0, x.stream));
+    HIPCHK(mcmc_post_accumulate(*x.slot, V, 0, x.stream));
     mcmc_post_counted(*x.slot);
     return 0;
 }
@@ -301,12 +278,12 @@ extern "C" int mceik_mcmc_posterior_get(mceik_mcmc *s, long long *n, long long *
     if (mcmc_post_ctx(s, &x) || !*x.slot) return 1;
     const McmcPost *p = *x.slot;
     if (mceik_mcmc_sync(s)) return -1;
-    PostScope dg(x.device);
+    DeviceScope dg(x.device);
     const size_t m = post_rows(p) * p->ncm;
     if (n) *n = p->n;
-    if (sum) PHIPCHK(hipMemcpy(sum, p->P.sum, m * 8, hipMemcpyDeviceToHost));
-    if (sumsq) PHIPCHK(hipMemcpy(sumsq, p->P.sumsq, m * 8, hipMemcpyDeviceToHost));
-    if (hist && p->P.nbins) PHIPCHK(hipMemcpy(hist, p->P.hist, (size_t)p->ncm * p->P.nbins * 4, hipMemcpyDeviceToHost));
+    if (sum) HIPCHK(hipMemcpy(sum, p->P.sum, m * 8, hipMemcpyDeviceToHost));
+    if (sumsq) HIPCHK(hipMemcpy(sumsq, p->P.sumsq, m * 8, hipMemcpyDeviceToHost));
+    if (hist && p->P.nbins) HIPCHK(hipMemcpy(hist, p->P.hist, (size_t)p->ncm * p->P.nbins * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -317,12 +294,12 @@ extern "C" int mceik_mcmc_posterior_set(mceik_mcmc *s, long long n, const long l
     if (mcmc_post_ctx(s, &x) || !*x.slot) return 1;
     McmcPost *p = *x.slot;
     if (n < 0 || !sum || !sumsq || (p->P.nbins && !hist)) return 1;
-    PostScope dg(x.device);
+    DeviceScope dg(x.device);
     const size_t m = post_rows(p) * p->ncm;
-    PHIPCHK(hipStreamSynchronize(x.stream));
-    PHIPCHK(hipMemcpy(p->P.sum, sum, m * 8, hipMemcpyHostToDevice));
-    PHIPCHK(hipMemcpy(p->P.sumsq, sumsq, m * 8, hipMemcpyHostToDevice));
-    if (p->P.nbins) PHIPCHK(hipMemcpy(p->P.hist, hist, (size_t)p->ncm * p->P.nbins * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipStreamSynchronize(x.stream));
+    HIPCHK(hipMemcpy(p->P.sum, sum, m * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(p->P.sumsq, sumsq, m * 8, hipMemcpyHostToDevice));
+    if (p->P.nbins) HIPCHK(hipMemcpy(p->P.hist, hist, (size_t)p->ncm * p->P.nbins * 4, hipMemcpyHostToDevice));
     p->n = n;
     return 0;
 }
@@ -335,20 +312,20 @@ extern "C" int mceik_mcmc_posterior_partials(mceik_mcmc *s, mceik_posterior_part
     if (!out->S || !out->Q || !out->P || (p->P.nbins && !out->hist)) return 1;
     const int ncm = p->ncm;
     {
-        PostScope dg(x.device);
+        DeviceScope dg(x.device);
         hipLaunchKernelGGL(post_reduce_kernel, dim3((ncm + 63) / 64), dim3(64), 0, x.stream, p->P, x.ncold, ncm,
                            p->d_S, p->d_Q, p->d_P);
-        PHIPCHK(hipGetLastError());
+        HIPCHK(hipGetLastError());
     }
     if (mceik_mcmc_sync(s)) return -1;
-    PostScope dg(x.device);
-    PHIPCHK(hipMemcpy(out->S, p->d_S, (size_t)ncm * 8, hipMemcpyDeviceToHost));
-    PHIPCHK(hipMemcpy(out->Q, p->d_Q, (size_t)ncm * 16, hipMemcpyDeviceToHost));
-    PHIPCHK(hipMemcpy(out->P, p->d_P, (size_t)ncm * 16, hipMemcpyDeviceToHost));
+    DeviceScope dg(x.device);
+    HIPCHK(hipMemcpy(out->S, p->d_S, (size_t)ncm * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out->Q, p->d_Q, (size_t)ncm * 16, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out->P, p->d_P, (size_t)ncm * 16, hipMemcpyDeviceToHost));
     if (p->P.nbins) {
         const size_t nh = (size_t)ncm * p->P.nbins;
         std::vector<unsigned> h(nh);
-        PHIPCHK(hipMemcpy(h.data(), p->P.hist, nh * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(h.data(), p->P.hist, nh * 4, hipMemcpyDeviceToHost));
         for (size_t k = 0; k < nh; k++) out->hist[k] = h[k];
     }
     out->ncm = ncm;

@@ -1,7 +1,7 @@
 // rccl_rt.h -- RCCL opened on first use (dlopen "librccl.so.1", the library
 // torch's nccl backend loads), shared by the sampler's checkpoint gather
 // (comm.hip) and the halo exchange of the block-decomposed solve across ranks
-// (capi.hip).  The product library carries no link dependency on RCCL, and
+// (dropin.hip).  The product library carries no link dependency on RCCL, and
 // single-GPU callers never load it.  Not a public header.
 #pragma once
 #include <dlfcn.h>

@@ -1,0 +1,119 @@
+// sampler.h -- the per-GPU MCMC sampler's host state (include/mceik.h
+// mceik_mcmc; not public), shared by sampler.hip (init, pipes, step loop,
+// finalize) and sampler_api.hip (accessors, tempering and block entry points).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+
+#include <vector>
+
+#include "../../include/mceik.h"
+#include "block.h"
+#include "fsm_common.h"
+#include "posterior.h"
+
+#define MCEIK_EV_RING 32           // hipEvent pairs around timed FSM launches (fixed ring)
+#define MCEIK_MAX_PIPES 4
+#define MCEIK_ITERS_N (6 + MCEIK_TRAFFIC_N)   // d_iters: iterations, 4 visit statistics, solves, traffic
+
+// A pipe: a part of the chains stepped on a stream of its own.  D, B and fb
+// are views of the sampler's D, B and fb restricted to the pipe's chains;
+// pipes_refresh alone writes them.
+struct Pipe {
+    McmcDev D;
+    BlockDev B;
+    mceik_fsm_batch fb;
+    void *ws;                          // the pipe's workspace: a part of the sampler's ws, ws itself, or its own
+    size_t ws_bytes;
+    bool ws_own;                       // ws was allocated for the pipe
+    hipStream_t st;                    // made with more than one pipe only: one pipe steps on the sampler's stream
+    hipEvent_t join;
+};
+
+struct mceik_mcmc {
+    McmcDev D;
+    hipEvent_t ev[2 * MCEIK_EV_RING];  // pairs around FSM launches (timing)
+    int ev_made;                       // pairs created so far
+    long long nlaunch;                 // timed launches since the last reset
+    long long ev_folded;               // launches whose pair has been folded into fsm_ms
+    double fsm_ms;                     // folded kernel time (ms)
+    unsigned long long *d_iters;
+    int *d_ierr;
+    unsigned long long *d_clock;       // per-solve start/end stamps of the last launch (queue order, report)
+    int *d_order;                      // longest-first queue order for the next launch (MCEIK_LPT=1), or null
+    bool report;                       // MCEIK_SOLVE_CLOCK_REPORT=1
+    // Two pipes (default; MCEIK_PIPES=1 turns them off): the chains run as two
+    // halves on two streams of their own, each half's next FSM launch queued
+    // behind its own accept, so one half's launch fills the waves the other
+    // half's queue tail leaves idle.  Results are those of
+    // one pipe bit for bit.  npipe >= 1 once init has set the pipes up: one pipe
+    // is pipe[0] viewing every chain, with the sampler's workspace and stream.
+    int npipe;
+    Pipe pipe[MCEIK_MAX_PIPES];
+    hipEvent_t pfork;
+    // Multi-step launches (MCEIK_PERSIST=1, where the 16-z kernel runs): one
+    // FSM launch runs up to MCEIK_MC_CHUNK steps, the
+    // chain epilogue (accept, kept state, next proposal) inside the kernel
+    // (fsm16_kernel.hip mc_finish), so no step waits for the slowest chain of
+    // the one before.  d_dev: device copy of D; d_sync: the launch's queues.
+    bool persist;
+    unsigned spin_limit;               // multi-step launches: polls before a wait counts as a broken queue
+    McmcDev *d_dev;
+    unsigned *d_sync;
+    mceik_fsm_batch fb;                // a step's batch: every chain's proposed model x stations
+    mceik_fsm_batch fb_all;            // init / restore: every model of every chain (= fb with one model)
+    const float *last_ttab;            // tables of the last forward (mceik_mcmc_last)
+    int masked_s;                      // S picks ignored (nphase 1, mask_s)
+    int device, max_samples, nburn, keepk, nkept, niter_total;
+    int nkept_base;                    // nkept at the last restore: earlier states are not in the ring
+    long long step;
+    McmcPost *post;                    // streaming posterior accumulators (posterior.hip), or null
+    // Parallel tempering (temper.hip); ntemps = 0: off.  Rung r
+    // of replica group g is chain r * G + g (G = nchains / ntemps), so the cold
+    // chains are [0, G).  Before the proposal of step gs > 0 with gs %
+    // swap_every == 0 a swap round of parity (gs / swap_every) & 1 runs.
+    int ntemps, swap_every;
+    std::vector<double> beta;          // the ladder [ntemps]
+    double *d_beta;                    // [nchains] the chains' beta (D.beta while ntemps > 1)
+    int *d_tflag;                      // [nchains] the round's swap flag per pair
+    unsigned long long *d_tcnt;        // [2][nchains] attempts, accepts per rung pair
+    // Block proposals (block.hip); off by default.  B holds the
+    // cell grid from init on; while on, every step takes the per-step branch
+    // with block.hip's two kernels in place of propose / accept.
+    bool block_on;
+    BlockDev B;
+    unsigned long long *d_bcnt;        // [2][MCEIK_BLOCK_RMAX + 1] attempts, accepts by radius
+    hipStream_t stream;
+    void *ws;
+    size_t ws_bytes;
+    std::vector<void *> allocs;
+};
+
+template <typename T>
+static int dalloc(mceik_mcmc *s, T **p, size_t count)
+{
+    void *q = nullptr;
+    if (hipMalloc(&q, count * sizeof(T) + 16) != hipSuccess) return -1;
+    hipMemset(q, 0, count * sizeof(T) + 16);
+    s->allocs.push_back(q);
+    *p = (T *)q;
+    return 0;
+}
+
+template <typename T>
+static int dput(mceik_mcmc *s, T **p, const T *host, size_t count)
+{
+    if (dalloc(s, p, count)) return -1;
+    if (count && hipMemcpy(*p, host, count * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return -1;
+    return 0;
+}
+
+// sampler.hip, as sampler_api.hip uses it
+int fold_launch(mceik_mcmc *s, long long k);
+int mcmc_forward_all(mceik_mcmc *s);
+int check_forward_ierr(mceik_mcmc *s, const char *who);
+int temper_cold(const mceik_mcmc *s);
+int temper_round(mceik_mcmc *s, int parity);
+// Recomputes every pipe's D, B and fb from the sampler's (and a multi-step
+// sampler's device copy of D): call after any change to s->D, s->B or s->fb.
+int pipes_refresh(mceik_mcmc *s);

@@ -1,0 +1,416 @@
+// sampler_api.hip -- the sampler's accessors of the C-ABI (include/mceik.h:
+// sync, state, checkpoint / restore, kept samples, info, FSM statistics) and
+// its parallel-tempering and block-proposal entry points.  The sampler itself
+// is sampler.hip.
+#include <hip/hip_runtime.h>
+#include <float.h>
+#include <limits.h>
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "fsm_batch.h"
+#include "fsm_host.h"
+#include "host_util.h"
+#include "mcmc_host.h"
+#include "sampler.h"
+
+// ---------------------------------------------------------------------------
+// parallel tempering (include/mceik.h mceik_mcmc_temper_*)
+
+extern "C" int mceik_temper_ladder(int ntemps, double tmax, double *beta)
+{
+    if (ntemps < 1 || !beta || !(tmax >= 1.0) || !(tmax <= DBL_MAX)) return 1;
+    beta[0] = 1.0;
+    for (int r = 1; r < ntemps; r++) beta[r] = pow(tmax, -(double)r / (double)(ntemps - 1));
+    return 0;
+}
+
+extern "C" int mceik_mcmc_temper_enable(mceik_mcmc *s, const mceik_temper_opts *o)
+{
+    if (!s || !o || !o->beta || o->ntemps < 1 || o->swap_every < 0) return 1;
+    const int nch = s->D.nchains, nt = o->ntemps;
+    if (nch % nt != 0 || o->beta[0] != 1.0) return 1;
+    for (int r = 0; r + 1 < nt; r++)
+        if (!(o->beta[r + 1] > 0.0 && o->beta[r + 1] <= o->beta[r])) return 1;
+    if (s->post && mcmc_post_count(s->post) > 0) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    if (!s->d_beta && (dalloc(s, &s->d_beta, nch) || dalloc(s, &s->d_tflag, nch) || dalloc(s, &s->d_tcnt, 2 * (size_t)nch)))
+        return -1;
+    const int G = nch / nt;
+    std::vector<double> bc(nch);
+    for (int c = 0; c < nch; c++) bc[c] = o->beta[c / G];
+    HIPCHK(hipMemcpy(s->d_beta, bc.data(), (size_t)nch * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(s->d_tcnt, 0, 2 * (size_t)nch * 8));
+    s->beta.assign(o->beta, o->beta + nt);
+    s->ntemps = nt;
+    s->swap_every = o->swap_every;
+    s->D.beta = nt > 1 ? s->d_beta : nullptr;       // one rung is the untempered sampler
+    return pipes_refresh(s);            // D.beta changed
+}
+
+extern "C" int mceik_mcmc_temper_disable(mceik_mcmc *s)
+{
+    if (!s) return 1;
+    if (!s->ntemps) return 0;
+    if (s->post && mcmc_post_count(s->post) > 0) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    s->ntemps = 0;
+    s->swap_every = 0;
+    s->beta.clear();
+    s->D.beta = nullptr;
+    return pipes_refresh(s);            // D.beta changed
+}
+
+extern "C" int mceik_mcmc_temper_get(mceik_mcmc *s, int *ntemps, int *swap_every, double *beta)
+{
+    if (!s || !s->ntemps) return 1;
+    if (ntemps) *ntemps = s->ntemps;
+    if (swap_every) *swap_every = s->swap_every;
+    if (beta) memcpy(beta, s->beta.data(), (size_t)s->ntemps * 8);
+    return 0;
+}
+
+extern "C" int mceik_mcmc_temper_stats(mceik_mcmc *s, long long *attempts, long long *accepts, int reset)
+{
+    if (!s || !s->ntemps) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    const size_t n = (size_t)(s->ntemps - 1) * 8;
+    if (attempts && n) HIPCHK(hipMemcpy(attempts, s->d_tcnt, n, hipMemcpyDeviceToHost));
+    if (accepts && n) HIPCHK(hipMemcpy(accepts, s->d_tcnt + s->D.nchains, n, hipMemcpyDeviceToHost));
+    if (reset) HIPCHK(hipMemset(s->d_tcnt, 0, 2 * (size_t)s->D.nchains * 8));
+    return 0;
+}
+
+extern "C" int mceik_mcmc_temper_swap(mceik_mcmc *s, int parity)
+{
+    if (!s || !s->ntemps || (parity != 0 && parity != 1)) return 1;
+    DeviceScope dg(s->device);
+    return temper_round(s, parity);
+}
+
+// ---------------------------------------------------------------------------
+// block proposals (include/mceik.h mceik_mcmc_block_*)
+
+extern "C" int mceik_mcmc_block_enable(mceik_mcmc *s, const mceik_block_opts *o)
+{
+    if (!s || !o || o->rmin < 0 || o->rmax < o->rmin || o->rmax > MCEIK_BLOCK_RMAX) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    const int nch = s->D.nchains, nr = MCEIK_BLOCK_RMAX + 1;
+    if (!s->d_bcnt) {                  // all three or none: a failed enable leaves the sampler as it was
+        unsigned long long *cnt = nullptr;
+        int *amp = nullptr, *rad = nullptr;
+        if (dalloc(s, &cnt, 2 * (size_t)nr) || dalloc(s, &amp, nch) || dalloc(s, &rad, nch)) return -1;
+        s->d_bcnt = cnt;
+        s->B.prop_amp = amp;
+        s->B.prop_rad = rad;
+    }
+    HIPCHK(hipMemset(s->d_bcnt, 0, 2 * (size_t)nr * 8));
+    s->B.rmin = o->rmin;
+    s->B.rmax = o->rmax;
+    s->B.attempts = s->d_bcnt;
+    s->B.accepts = s->d_bcnt + nr;
+    s->block_on = true;
+    return pipes_refresh(s);
+}
+
+extern "C" int mceik_mcmc_block_disable(mceik_mcmc *s)
+{
+    if (!s) return 1;
+    if (!s->block_on) return 0;
+    s->block_on = false;               // host state only: queued steps keep the kernels they were queued with
+    DeviceScope dg(s->device);
+    return pipes_refresh(s);
+}
+
+extern "C" int mceik_mcmc_block_get(mceik_mcmc *s, int *rmin, int *rmax)
+{
+    if (!s || !s->block_on) return 1;
+    if (rmin) *rmin = s->B.rmin;
+    if (rmax) *rmax = s->B.rmax;
+    return 0;
+}
+
+extern "C" int mceik_mcmc_block_stats(mceik_mcmc *s, long long *attempts, long long *accepts, int reset)
+{
+    if (!s || !s->block_on) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    const int nr = MCEIK_BLOCK_RMAX + 1;
+    const size_t n = (size_t)(s->B.rmax + 1) * 8;
+    if (attempts) HIPCHK(hipMemcpy(attempts, s->B.attempts, n, hipMemcpyDeviceToHost));
+    if (accepts) HIPCHK(hipMemcpy(accepts, s->B.accepts, n, hipMemcpyDeviceToHost));
+    if (reset) HIPCHK(hipMemset(s->d_bcnt, 0, 2 * (size_t)nr * 8));
+    return 0;
+}
+
+extern "C" int mceik_block_footprint(int ncx, int ncy, int ncz, int cell, int radius, int amp, int *cells, int *dv)
+{
+    if (ncx < 1 || ncy < 1 || ncz < 1 || (long long)ncx * ncy * ncz > INT_MAX || cell < 0 || cell >= ncx * ncy * ncz ||
+        radius < 0 || radius > MCEIK_BLOCK_RMAX || amp == 0 || amp == INT_MIN)
+        return -1;
+    const int cx = cell % ncx, cy = (cell / ncx) % ncy, cz = cell / (ncx * ncy);
+    const int mag = amp < 0 ? -amp : amp, n = 2 * radius + 1;
+    int cnt = 0;
+    for (int k = 0; k < n * n * n; k++) {
+        int t = 0;
+        const int d = block_dv(ncx, ncy, ncz, cx, cy, cz, radius, mag, k, &t);
+        if (!d) continue;
+        if (cells) cells[cnt] = t;
+        if (dv) dv[cnt] = amp < 0 ? -d : d;
+        cnt++;
+    }
+    return cnt;
+}
+
+int mcmc_post_ctx(mceik_mcmc *s, McmcPostCtx *out)
+{
+    if (!s || !out) return 1;
+    out->device = s->device;
+    out->stream = s->stream;
+    out->D = &s->D;
+    out->slot = &s->post;
+    out->ncold = temper_cold(s);
+    return 0;
+}
+
+// After a stream synchronisation: a multi-step launch whose wave gave up
+// waiting for a chain's step (the broken-queue flag) failed, and the chains'
+// state is not to be trusted; every later synchronising call (and the
+// gather, through mcmc_shard_view) reports it until mceik_mcmc_restore
+// reloads a state.
+static int mc_queue_check(mceik_mcmc *s, const char *who)
+{
+    if (!s->persist) return 0;
+    unsigned flag = 0;
+    HIPCHK(hipMemcpy(&flag, s->d_sync + MC_SYNC_WORDS(s->D.nchains) - 1, sizeof(flag), hipMemcpyDeviceToHost));
+    if (!flag) return 0;
+    fprintf(stderr, "%s: a multi-step launch timed out waiting for a chain's previous step (broken work queue); "
+                    "the chain state is invalid\n", who);
+    return -1;
+}
+
+extern "C" int mceik_mcmc_sync(mceik_mcmc *s)
+{
+    if (!s) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return mc_queue_check(s, "mceik_mcmc_sync");
+}
+
+extern "C" int mceik_mcmc_get_state(mceik_mcmc *s, int *v, double *logl, long long *naccept, long long *step)
+{
+    if (!s) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    if (mc_queue_check(s, "mceik_mcmc_get_state")) return -1;
+    const McmcDev &D = s->D;
+    if (v) HIPCHK(hipMemcpy(v, D.v, (size_t)D.nchains * D.ncm * 4, hipMemcpyDeviceToHost));
+    if (logl) HIPCHK(hipMemcpy(logl, D.logl, (size_t)D.nchains * 8, hipMemcpyDeviceToHost));
+    if (naccept) HIPCHK(hipMemcpy(naccept, D.naccept, (size_t)D.nchains * 8, hipMemcpyDeviceToHost));
+    if (step) *step = s->step;
+    return 0;
+}
+
+extern "C" int mceik_mcmc_checkpoint(mceik_mcmc *s, int *v, double *logl, long long *naccept, long long *step,
+                                     int *nkept)
+{
+    if (!s) return 1;
+    if (mceik_mcmc_get_state(s, v, logl, naccept, step)) return -1;
+    if (nkept) *nkept = s->nkept;
+    return 0;
+}
+
+extern "C" int mceik_mcmc_restore(mceik_mcmc *s, const int *v, const double *logl, const long long *naccept,
+                                  long long step, int nkept)
+{
+    if (!s || !v || step < 0 || nkept < 0) return 1;
+    DeviceScope dg(s->device);
+    McmcDev &D = s->D;
+    const size_t n = (size_t)D.nchains * D.ncm;
+    for (size_t i = 0; i < n; i++) {
+        const bool sph = (int)(i % (size_t)D.ncm) >= D.ncell;
+        const int lo = sph ? D.vsmin : D.vmin, hi = sph ? D.vsmax : D.vmax;
+        if (v[i] < lo || v[i] > hi) {
+            fprintf(stderr, "mceik_mcmc_restore: v[%zu] = %d outside the prior [%d, %d]\n", i, v[i], lo, hi);
+            return 1;
+        }
+    }
+    std::vector<float> sl(n);
+    for (size_t i = 0; i < n; i++) sl[i] = 1.0f / (float)v[i];
+    HIPCHK(hipStreamSynchronize(s->stream));
+    HIPCHK(hipMemcpy(D.v, v, n * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(D.slow_cur, sl.data(), n * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(D.slow_prop, sl.data(), n * sizeof(float), hipMemcpyHostToDevice));
+    if (naccept) HIPCHK(hipMemcpy(D.naccept, naccept, (size_t)D.nchains * 8, hipMemcpyHostToDevice));
+    else HIPCHK(hipMemset(D.naccept, 0, (size_t)D.nchains * 8));
+    if (logl) {
+        HIPCHK(hipMemcpy(D.logl, logl, (size_t)D.nchains * 8, hipMemcpyHostToDevice));
+    } else {
+        // one forward of the restored models (not timed, not counted in the FSM stats)
+        unsigned long long keep[MCEIK_ITERS_N];
+        HIPCHK(hipMemcpy(keep, s->d_iters, sizeof(keep), hipMemcpyDeviceToHost));
+        if (mcmc_forward_all(s)) return -1;
+        HIPCHK(mcmc_init_loglik(D, s->stream));
+        HIPCHK(hipStreamSynchronize(s->stream));
+        HIPCHK(hipMemcpy(s->d_iters, keep, sizeof(keep), hipMemcpyHostToDevice));
+        if (check_forward_ierr(s, "mceik_mcmc_restore")) return 2;
+    }
+    s->step = step;
+    s->nkept = nkept;
+    s->nkept_base = nkept;
+    if (s->persist) {
+        // the restored state replaces whatever a broken multi-step launch left: clear its flag
+        HIPCHK(hipMemset(s->d_sync + MC_SYNC_WORDS(s->D.nchains) - 1, 0, sizeof(unsigned)));
+    }
+    return 0;
+}
+
+extern "C" int mceik_mcmc_get_samples(mceik_mcmc *s, void *v_out, double *logl_out, int max, int kind, int *nkept)
+{
+    if (!s) return 1;
+    int have = std::min(s->nkept - s->nkept_base, s->max_samples);
+    int n = have < max ? have : max;
+    if (nkept) *nkept = n;
+    if (n <= 0) return 0;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    if (mc_queue_check(s, "mceik_mcmc_get_samples")) return -1;
+    hipMemcpyKind k = kind ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    const size_t per = (size_t)s->D.nchains * s->D.ncm;
+    // ring slot of the i-th of the n most recent states: (nkept - n + i) mod max_samples
+    int i = 0;
+    while (i < n) {
+        const int slot = (int)(((long long)s->nkept - n + i) % s->max_samples);
+        const int run = std::min(n - i, s->max_samples - slot);     // contiguous slots
+        if (v_out)
+            HIPCHK(hipMemcpy((int *)v_out + (size_t)i * per, s->D.keep_v + (size_t)slot * per,
+                             (size_t)run * per * 4, k));
+        if (logl_out)
+            HIPCHK(hipMemcpy(logl_out + (size_t)i * s->D.nchains, s->D.keep_logl + (size_t)slot * s->D.nchains,
+                             (size_t)run * s->D.nchains * 8, k));
+        i += run;
+    }
+    return 0;
+}
+
+// Device view of this sampler's chain shard for comm.hip's gather: which = 0
+// the current state, 1 the most recent kept state (1 if none is kept).
+int mcmc_shard_view(mceik_mcmc *s, int which, McmcShard *out)
+{
+    if (!s || !out) return 1;
+    const McmcDev &D = s->D;
+    out->device = s->device; out->stream = s->stream;
+    out->nchains = D.nchains; out->chain_offset = D.chain_offset; out->ncell = D.ncm;
+    {   // a broken multi-step launch left no valid state to gather (-1)
+        DeviceScope dg(s->device);
+        if (hipStreamSynchronize(s->stream) != hipSuccess || mc_queue_check(s, "mceik_mcmc_gather")) return -1;
+    }
+    if (which == 0) {
+        out->v = D.v; out->logl = D.logl;
+        return 0;
+    }
+    if (s->max_samples <= 0 || s->nkept - s->nkept_base <= 0) return 1;
+    const int slot = (int)(((long long)s->nkept - 1) % s->max_samples);
+    out->v = D.keep_v + (size_t)slot * D.nchains * D.ncm;
+    out->logl = D.keep_logl + (size_t)slot * D.nchains;
+    return 0;
+}
+
+extern "C" int mceik_mcmc_last(mceik_mcmc *s, const float **ttab, const int **niter, const unsigned char **accept,
+                               const int **ierr)
+{
+    if (!s) return 1;
+    if (ttab) *ttab = s->last_ttab;
+    if (niter) *niter = s->fb.niter;
+    if (accept) *accept = s->D.accept;
+    if (ierr) *ierr = s->d_ierr;
+    return 0;
+}
+
+extern "C" int mceik_mcmc_last_phase(mceik_mcmc *s, const int **phase)
+{
+    if (!s || !phase) return 1;
+    *phase = s->D.prop_phase;
+    return 0;
+}
+
+extern "C" int mceik_mcmc_get_info(mceik_mcmc *s, mceik_mcmc_info *info)
+{
+    if (!s || !info) return 1;
+    DeviceScope dg(s->device);
+    memset(info, 0, sizeof(*info));
+    info->npipe = s->npipe;
+    info->multi_step = s->persist && !s->block_on ? 1 : 0;   // block proposals step per launch
+    info->nphase = s->D.nphase;
+    info->masked_s = s->masked_s;
+    FsmLaunch L;
+    fill_launch(L, &s->fb);
+    const int is_double = s->fb.precision == 64;
+    info->step_z = fsm_launch_kind(L, is_double);
+    info->fixed_layout = info->step_z == 16 && fsm16_fixed_layout(L) ? 1 : 0;
+    info->lds_bytes = fsm_launch_lds_bytes(L, is_double);
+    snprintf(info->kernel, sizeof(info->kernel), "%s", fsm_launch_name(L, is_double));
+    for (int k = 0; k < s->npipe && k < 4; k++) {
+        const Pipe &p = s->pipe[k];
+        info->chains[k] = p.fb.nmodel;
+        info->waves[k] = ws_layout(&p.fb).nwaves;
+        info->workspace_bytes[k] = p.ws_bytes;
+    }
+    return 0;
+}
+
+extern "C" int mceik_mcmc_fsm_stats(mceik_mcmc *s, double *fsm_ms, long long *nlaunch, unsigned long long *iters,
+                                    unsigned long long *visits, int reset)
+{
+    if (!s) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    if (mc_queue_check(s, "mceik_mcmc_fsm_stats")) return -1;
+    while (s->ev_folded < s->nlaunch) {
+        if (fold_launch(s, s->ev_folded)) return -1;
+        s->ev_folded++;
+    }
+    unsigned long long it[MCEIK_ITERS_N] = {0};
+    HIPCHK(hipMemcpy(it, s->d_iters, sizeof(it), hipMemcpyDeviceToHost));
+    {   // accounting build: requested bytes per launch by category
+        unsigned long long tsum = 0;
+        for (int k = 0; k < MCEIK_TRAFFIC_N; k++) tsum += it[6 + k];
+        if (tsum && s->nlaunch) {
+            static const char *nm[MCEIK_TRAFFIC_N] = {"own_load", "halo_load", "zup_load", "own_store",
+                                                      "u0_store", "cell_load", "verify_load", "init_gather"};
+            fprintf(stderr, "mceik traffic (requested bytes per FSM launch, %lld launches):", s->nlaunch);
+            for (int k = 0; k < MCEIK_TRAFFIC_N; k++) fprintf(stderr, " %s=%.6e", nm[k], (double)it[6 + k] / s->nlaunch);
+            fprintf(stderr, " total=%.6e\n", (double)tsum / s->nlaunch);
+        }
+    }
+    if (fsm_ms) *fsm_ms = s->fsm_ms;
+    if (nlaunch) *nlaunch = s->nlaunch;
+    if (iters) *iters = it[0];
+    if (visits) { visits[0] = it[1]; visits[1] = it[2]; visits[2] = it[3]; visits[3] = it[4]; }
+    if (reset) {
+        s->fsm_ms = 0.0;
+        s->nlaunch = 0;
+        s->ev_folded = 0;
+        HIPCHK(hipMemset(s->d_iters, 0, MCEIK_ITERS_N * sizeof(unsigned long long)));
+    }
+    return 0;
+}
+
+extern "C" int mceik_mcmc_fsm_solves(mceik_mcmc *s, unsigned long long *solves)
+{
+    if (!s || !solves) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    if (mc_queue_check(s, "mceik_mcmc_fsm_solves")) return -1;
+    HIPCHK(hipMemcpy(solves, s->d_iters + 5, sizeof(*solves), hipMemcpyDeviceToHost));
+    return 0;
+}

@@ -123,7 +123,7 @@ class Problem:
     def ev_cell(self):
         """Trilinear mode (tt_interp = 1): (lowest corner node [nev] int32, fractions
         [nev][3] float32) of each event's grid cell, as mceik_mcmc_init computes them
-        (capi.hip cell_corner: i = trunc((x - x0)/h) clamped to [0, n-2], w = f - i in
+        (sampler.hip cell_corner: i = trunc((x - x0)/h) clamped to [0, n-2], w = f - i in
         [0, 1] rounded once to fp32)."""
         def corner(n, x0, xs):
             f = (np.asarray(xs, dtype=np.float64) - x0) / self.h

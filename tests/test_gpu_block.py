@@ -172,12 +172,16 @@ def _restate(p, v0, logl0, off, nsteps, rmin, rmax, precision=32, betas=None, sw
                                  events=events)
 
 
-def _run_gpu(p, nch, off, nsteps, block, precision=32, betas=None, swap_every=0, path=None):
-    smp = _sampler(p, nch, block=block, chain_offset=off, precision=precision)
-    if path is not None:
-        _check_path(smp, path, block=True)
+def _run_gpu(p, nch, off, nsteps, block, precision=32, betas=None, swap_every=0, path=None, order="block_first"):
+    """order: block_enable before temper_enable ("block_first") or after it ("temper_first")."""
+    assert order in ("block_first", "temper_first")
+    smp = _sampler(p, nch, block=block if order == "block_first" else None, chain_offset=off, precision=precision)
     if betas is not None:
         smp.temper_enable(betas=betas, swap_every=swap_every)
+    if order == "temper_first":
+        smp.block_enable(*block)
+    if path is not None:
+        _check_path(smp, path, block=True)
     v0, l0, _, _ = smp.state()
     smp.run(nsteps)
     out = types.SimpleNamespace()
@@ -299,18 +303,56 @@ def test_precision_64(monkeypatch):
 
 
 # --- 5. tempering with block proposals ---
-def test_tempering_with_block_proposals(monkeypatch):
+# 9 chains, 3 rungs: G = 3, and two pipes split at chain 4, inside a replica group.  Either order of the two
+# enables must leave every pipe's view with both the block arrays and beta.
+_TEMPERED = {}          # path -> (v0, l0, restatement): the start state does not depend on the order
+
+
+@pytest.mark.parametrize("order", ["block_first", "temper_first"])
+@pytest.mark.parametrize("path", ["per_step", "two_pipes"])
+def test_tempering_with_block_proposals(path, order, monkeypatch):
     _dev()
-    p = _problem("P", n=_set_path("per_step", monkeypatch))
+    p = _problem("P", n=_set_path(path, monkeypatch))
     nch, off, nsteps = 9, 5, 5
-    g = _run_gpu(p, nch, off, nsteps, (0, 2), betas=LADDER3, swap_every=2)
-    r = _restate(p, g.v0, g.l0, off, nsteps, 0, 2, betas=LADDER3, swap_every=2)
+    g = _run_gpu(p, nch, off, nsteps, (0, 2), betas=LADDER3, swap_every=2, path=path, order=order)
+    if path not in _TEMPERED:
+        _TEMPERED[path] = (g.v0, g.l0, _restate(p, g.v0, g.l0, off, nsteps, 0, 2, betas=LADDER3, swap_every=2))
+    v0, l0, r = _TEMPERED[path]
+    _same((g.v0, g.l0), (v0, l0), "start state")
     # rounds at gs = 2 (parity 1) and 4 (parity 0): a swap after rejected and accepted block steps moves
     # slow_prop rows that must equal slow_cur, or the next forward solves a stale model
     assert r.swap_att.tolist() == [3, 3] and r.swap_acc.sum() > 0
     assert any(e.acc and e.R >= 1 for e in r.events) and any(e.inp and not e.acc and e.R >= 1 for e in r.events)
     _compare(g, r, nsteps, "tempered")
     _same((g.swap_att, g.swap_acc), (r.swap_att, r.swap_acc), "swap counters")
+
+
+def test_tempering_and_blocks_switched_off_two_pipes_is_one_pipe(monkeypatch):
+    """Block proposals and tempering on, 2 steps, tempering off, 2 steps, block proposals off, 2 steps: two pipes
+    and one pipe give the same words (every pipe's view follows each switch)."""
+    _dev()
+    p = _problem("P", n=_set_path("two_pipes", monkeypatch))
+    nch, off = 9, 5
+
+    def run(npipe):
+        monkeypatch.setenv("MCEIK_PIPES", str(npipe))
+        s = _sampler(p, nch, block=(0, 2), chain_offset=off, max_samples=8)
+        assert s.info()["npipe"] == npipe and not s.info()["multi_step"], s.info()
+        s.temper_enable(betas=LADDER3, swap_every=2)
+        s.run(2)
+        s.temper_disable()
+        s.run(2)
+        s.block_disable()
+        s.run(2)
+        out = s.state() + s.samples()
+        s.close()
+        return out
+
+    two, one = run(2), run(1)
+    _same(two, one, "two pipes against one")
+    v, logl, nacc, step, kv, kl = two
+    assert step == 6 and nacc.sum() > 0 and len(kv) == 6
+    _same((kv[-1], kl[-1]), (v, logl), "the last kept state is the state after step 5")
 
 
 # --- 6. the streaming posterior sees block steps ---
