@@ -323,6 +323,64 @@ int mceik_mcmc_block_stats(mceik_mcmc *s, long long *attempts, long long *accept
  * touched count, -1 on invalid arguments. */
 int mceik_block_footprint(int ncx, int ncy, int ncz, int cell, int radius, int amp, int *cells, int *dv);
 
+/* ---- smoothness and reference-model prior (csrc/prior.hip) -
+ * Off by default; with it off nothing changes.  Besides the uniform box every
+ * chain's phase model (ncx x ncy x ncz inversion cells, x fastest) then carries
+ * two exact integer energies:
+ *   roughness Es = sum over face-adjacent cell pairs (i, j) of (v_i - v_j)^2
+ *             (pairs never join the P and the S model),
+ *   damping   Ed = sum_i (v_i - vref_i)^2 against vref[nphase * ncell], one
+ *             reference model shared by all chains (vref NULL: Ed = 0),
+ * and log prior = -(w_smooth[ph] Es + w_damp[ph] Ed): a Gaussian Markov random
+ * field truncated to the box.  The weights are finite and >= 0, w = 1 / (2
+ * sigma^2) with sigma in m/s; [0] is the P model's, [1] the S model's.
+ *
+ * Accept rule: for a pending proposal inside the box that touches phase ph,
+ * with dEs = Es(v') - Es(v) and dEd likewise (exact integers),
+ *   dlp = -(w_smooth[ph] * (double)dEs + w_damp[ph] * (double)dEd)
+ *   thr = log u - dlp
+ *   accept iff thr < logL' - logL     (tempering: thr < beta * (logL' - logL);
+ *                                      the prior is not tempered)
+ * in IEEE double without contraction.  With all weights zero thr == log u and
+ * the sampler is the plain one bit for bit.  Tempering's swap rule does not
+ * change: both replicas carry the untempered prior, which cancels.  logL and
+ * the kept logL stay the likelihood.
+ *
+ * enable refuses (1) a sampler where 3 ncell (hi - lo + 2 dvmax)^2 >= 2^53 for
+ * a phase's box [lo, hi] (below that every energy and difference converts to
+ * double exactly), a vref entry outside its phase's box, and a weight that is
+ * negative or not finite.  While enabled every step is one launch
+ * (mceik_mcmc_info.multi_step reports 0 until disable), with one more kernel
+ * between the proposal and the forward; a run gains no host synchronisation.
+ * enable / disable return 1 while an enabled posterior holds states.
+ *
+ * Every function returns 0, 1 on invalid arguments (NULL, not enabled, the
+ * refusals above) or -1 on a device failure. */
+typedef struct mceik_prior_opts { double w_smooth[2], w_damp[2]; const int *vref; } mceik_prior_opts;
+/* Turns the prior on (or replaces the weights and vref).  Synchronises. */
+int mceik_mcmc_prior_enable(mceik_mcmc *s, const mceik_prior_opts *o);
+/* Later steps are the plain sampler's again. */
+int mceik_mcmc_prior_disable(mceik_mcmc *s);
+/* The options in force (o may be NULL).  vref: host [nphase * ncell] or NULL;
+ * it is filled, and o->vref points to it, when a reference model is loaded,
+ * else o->vref is NULL. */
+int mceik_mcmc_prior_get(mceik_mcmc *s, mceik_prior_opts *o, int *vref);
+/* Es, Ed [nchains][nphase] of the chains' current models, summed on the GPU
+ * (either may be NULL).  Synchronises. */
+int mceik_mcmc_prior_energy(mceik_mcmc *s, long long *Es, long long *Ed);
+/* dE [nchains][2] = (dEs, dEd) of every chain's proposal of the last step,
+ * accepted or not; 0, 0 for a proposal outside the box.  Synchronises. */
+int mceik_mcmc_prior_last(mceik_mcmc *s, long long *dE);
+/* Host only (no GPU call), the arithmetic the kernels run.  energy: Es, Ed of
+ * one ncx x ncy x ncz model v (vref NULL: Ed = 0).  delta: their change under
+ * the block footprint (mceik_block_footprint) of signed amplitude amp != 0 and
+ * radius 0..8 centred on `cell`, evaluated on the unchanged v.  Outputs may be
+ * NULL.  Both return 1 on invalid arguments, and where 3 ncell span^2 >= 2^53
+ * with span the range of the values in v and vref (delta: plus 2 |amp|). */
+int mceik_prior_energy(int ncx, int ncy, int ncz, const int *v, const int *vref, long long *Es, long long *Ed);
+int mceik_prior_delta(int ncx, int ncy, int ncz, const int *v, const int *vref, int cell, int radius, int amp,
+                      long long *dEs, long long *dEd);
+
 /* ---- multi-rank runs (one process per GPU; csrc/comm.hip) ---------------
  * The sampler's only collective is the checkpoint gather (SURVEY s.8e) over
  * RCCL (xGMI on one node).  Bootstrap as RCCL's: rank 0 calls

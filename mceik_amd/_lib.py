@@ -109,6 +109,11 @@ class BlockOpts(C.Structure):
     _fields_ = [("rmin", C.c_int), ("rmax", C.c_int)]
 
 
+class PriorOpts(C.Structure):
+    """mceik_prior_opts (include/mceik.h)."""
+    _fields_ = [("w_smooth", C.c_double * 2), ("w_damp", C.c_double * 2), ("vref", C.c_void_p)]
+
+
 # every extern "C" symbol include/*.h declares
 EXPORTS = ("eikonal3d_serial_driver", "eikonal3d_serial_driver_sp", "eikonal3d_batch_solve", "eikonal3d_initialize", "eikonal3d_solve",
            "eikonal3d_finalize", "locate3d_gridsearch__double64", "locate3d_gridsearch__float64",
@@ -129,6 +134,8 @@ EXPORTS = ("eikonal3d_serial_driver", "eikonal3d_serial_driver_sp", "eikonal3d_b
            "mceik_mcmc_temper_stats", "mceik_mcmc_temper_swap", "mceik_temper_ladder",
            "mceik_mcmc_block_enable", "mceik_mcmc_block_disable", "mceik_mcmc_block_get", "mceik_mcmc_block_stats",
            "mceik_block_footprint",
+           "mceik_mcmc_prior_enable", "mceik_mcmc_prior_disable", "mceik_mcmc_prior_get", "mceik_mcmc_prior_energy",
+           "mceik_mcmc_prior_last", "mceik_prior_energy", "mceik_prior_delta",
            "mceik_parms_defaults", "mceik_parms_set", "mceik_parms_read", "mceik_parms_args", "mceik_parms_write",
            "mceik_comm_available", "mceik_comm_unique_id", "mceik_comm_init", "mceik_comm_finalize", "mceik_mcmc_gather",
            "os_path_exists", "os_path_isdir", "os_path_isfile", "os_makedirs", "os_mkdir")
@@ -258,5 +265,19 @@ def lib():
     L.mceik_mcmc_block_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.mceik_block_footprint.restype = C.c_int
     L.mceik_block_footprint.argtypes = [C.c_int] * 6 + [C.c_void_p, C.c_void_p]
+    L.mceik_mcmc_prior_enable.restype = C.c_int
+    L.mceik_mcmc_prior_enable.argtypes = [C.c_void_p, C.POINTER(PriorOpts)]
+    L.mceik_mcmc_prior_disable.restype = C.c_int
+    L.mceik_mcmc_prior_disable.argtypes = [C.c_void_p]
+    L.mceik_mcmc_prior_get.restype = C.c_int
+    L.mceik_mcmc_prior_get.argtypes = [C.c_void_p, C.POINTER(PriorOpts), C.c_void_p]
+    L.mceik_mcmc_prior_energy.restype = C.c_int
+    L.mceik_mcmc_prior_energy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mceik_mcmc_prior_last.restype = C.c_int
+    L.mceik_mcmc_prior_last.argtypes = [C.c_void_p, C.c_void_p]
+    L.mceik_prior_energy.restype = C.c_int
+    L.mceik_prior_energy.argtypes = [C.c_int] * 3 + [C.c_void_p] * 2 + [C.POINTER(C.c_longlong)] * 2
+    L.mceik_prior_delta.restype = C.c_int
+    L.mceik_prior_delta.argtypes = [C.c_int] * 3 + [C.c_void_p] * 2 + [C.c_int] * 3 + [C.POINTER(C.c_longlong)] * 2
     _lib = L
     return L

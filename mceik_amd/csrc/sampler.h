@@ -11,17 +11,19 @@
 #include "block.h"
 #include "fsm_common.h"
 #include "posterior.h"
+#include "prior.h"
 
 #define MCEIK_EV_RING 32           // hipEvent pairs around timed FSM launches (fixed ring)
 #define MCEIK_MAX_PIPES 4
 #define MCEIK_ITERS_N (6 + MCEIK_TRAFFIC_N)   // d_iters: iterations, 4 visit statistics, solves, traffic
 
-// A pipe: a part of the chains stepped on a stream of its own.  D, B and fb
-// are views of the sampler's D, B and fb restricted to the pipe's chains;
+// A pipe: a part of the chains stepped on a stream of its own.  D, B, P and fb
+// are views of the sampler's D, B, P and fb restricted to the pipe's chains;
 // pipes_refresh alone writes them.
 struct Pipe {
     McmcDev D;
     BlockDev B;
+    PriorDev P;
     mceik_fsm_batch fb;
     void *ws;                          // the pipe's workspace: a part of the sampler's ws, ws itself, or its own
     size_t ws_bytes;
@@ -83,6 +85,14 @@ struct mceik_mcmc {
     bool block_on;
     BlockDev B;
     unsigned long long *d_bcnt;        // [2][MCEIK_BLOCK_RMAX + 1] attempts, accepts by radius
+    // Smoothness / reference-model prior (prior.hip); off by
+    // default.  While on, every step takes the per-step branch with
+    // prior_fold between the proposal and the forward.
+    bool prior_on;
+    PriorDev P;
+    bool prior_vref;                   // a reference model is loaded (P.vref == d_vref)
+    int *d_vref;                       // [nphase][ncell]
+    unsigned long long *d_pen;         // [2][nchains * nphase] Es, Ed of mceik_mcmc_prior_energy
     hipStream_t stream;
     void *ws;
     size_t ws_bytes;
@@ -114,6 +124,6 @@ int mcmc_forward_all(mceik_mcmc *s);
 int check_forward_ierr(mceik_mcmc *s, const char *who);
 int temper_cold(const mceik_mcmc *s);
 int temper_round(mceik_mcmc *s, int parity);
-// Recomputes every pipe's D, B and fb from the sampler's (and a multi-step
-// sampler's device copy of D): call after any change to s->D, s->B or s->fb.
+// Recomputes every pipe's D, B, P and fb from the sampler's (and a multi-step
+// sampler's device copy of D): call after any change to s->D, s->B, s->P or s->fb.
 int pipes_refresh(mceik_mcmc *s);

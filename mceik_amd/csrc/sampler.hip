@@ -3,7 +3,8 @@
 // time, the pipes, the forward launch and the step loop.
 //
 // Host orchestration only.  The numerics live in fsm_kernel.hip,
-// fsm16_kernel.hip, mcmc_kernels.hip, temper.hip, block.hip and posterior.hip.
+// fsm16_kernel.hip, mcmc_kernels.hip, temper.hip, block.hip, prior.hip and
+// posterior.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -154,6 +155,14 @@ static BlockDev dev_view(const BlockDev &B, int off)
     return V;
 }
 
+// The same view of the prior state: dE is [nchains][2].
+static PriorDev dev_view(const PriorDev &P, int off)
+{
+    PriorDev V = P;
+    if (V.dE) V.dE += 2 * (size_t)off;
+    return V;
+}
+
 static mceik_fsm_batch batch_view(const mceik_fsm_batch &b, int off, int n, size_t ncm)
 {
     mceik_fsm_batch V = b;
@@ -180,6 +189,7 @@ int pipes_refresh(mceik_mcmc *s)
         const int lo = pipe_lo(nch, k, np), n = pipe_lo(nch, k + 1, np) - lo;
         p.D = dev_view(s->D, lo, n);
         p.B = dev_view(s->B, lo);
+        p.P = dev_view(s->P, lo);
         p.fb = batch_view(s->fb, lo, n, (size_t)s->D.ncm);
     }
     // the longest-first order covers the whole batch: one pipe's (mcmc_forward)
@@ -387,6 +397,7 @@ extern "C" int mceik_mcmc_init(const struct mceik_parms_struct *parms, const str
     D.vsmin = nphase == 2 ? o->vsmin : 0; D.vsmax = nphase == 2 ? o->vsmax : 0;
     memset(&s->B, 0, sizeof(s->B));
     s->B.ncx = ncx; s->B.ncy = ncy; s->B.ncz = ncz;
+    memset(&s->P, 0, sizeof(s->P));
     // host-side problem tables
     std::vector<double> src((size_t)nstat * 4);
     for (int i = 0; i < nstat; i++) {
@@ -621,8 +632,9 @@ int temper_round(mceik_mcmc *s, int parity)
 static int mcmc_steps(mceik_mcmc *s, int nsteps)
 {
     // block proposals: the multi-step kernel's epilogue is single-cell, so a
-    // sampler built for multi-step launches (one pipe) steps per launch
-    if (s->persist && !s->block_on) {
+    // sampler built for multi-step launches (one pipe) steps per launch; the
+    // prior's fold sits between a step's proposal and its forward, likewise
+    if (s->persist && !s->block_on && !s->prior_on) {
         // the first step's proposals here, then up to MCEIK_MC_CHUNK steps per
         // FSM launch (the kernel accepts, keeps and proposes the rest)
         for (int done = 0; done < nsteps;) {
@@ -678,6 +690,7 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
             const Pipe &p = s->pipe[k];
             const hipStream_t st = pipe_stream(s, k);
             HIPCHK(blk ? block_propose(p.D, p.B, step, st) : mcmc_propose(p.D, step, st));
+            if (s->prior_on) HIPCHK(prior_fold(p.D, p.B, p.P, blk, st));
             if (mcmc_forward(s, true, k)) return -1;
             HIPCHK(blk ? block_accept(p.D, p.B, slot, st) : mcmc_accept(p.D, slot, st));
             if (post)               // the pipe's rows of the accumulators, offset like its keep_v (dev_view)

@@ -1,7 +1,7 @@
 // sampler_api.hip -- the sampler's accessors of the C-ABI (include/mceik.h:
 // sync, state, checkpoint / restore, kept samples, info, FSM statistics) and
-// its parallel-tempering and block-proposal entry points.  The sampler itself
-// is sampler.hip.
+// its parallel-tempering, block-proposal and prior entry points.  The sampler
+// itself is sampler.hip.
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <limits.h>
@@ -169,6 +169,154 @@ extern "C" int mceik_block_footprint(int ncx, int ncy, int ncz, int cell, int ra
         cnt++;
     }
     return cnt;
+}
+
+// ---------------------------------------------------------------------------
+// smoothness / reference-model prior (include/mceik.h mceik_mcmc_prior_*)
+
+static bool prior_weight_ok(double w) { return w >= 0.0 && w <= DBL_MAX; }
+
+extern "C" int mceik_mcmc_prior_enable(mceik_mcmc *s, const mceik_prior_opts *o)
+{
+    if (!s || !o) return 1;
+    const McmcDev &D = s->D;
+    for (int ph = 0; ph < 2; ph++)
+        if (!prior_weight_ok(o->w_smooth[ph]) || !prior_weight_ok(o->w_damp[ph])) return 1;
+    for (int ph = 0; ph < D.nphase; ph++) {
+        const long long lo = ph ? D.vsmin : D.vmin, hi = ph ? D.vsmax : D.vmax;
+        if (!prior_fits(D.ncell, hi - lo + 2LL * D.dvmax)) {
+            fprintf(stderr, "mceik_mcmc_prior_enable: 3 ncell (hi - lo + 2 dvmax)^2 >= 2^53 for the %s model: the "
+                            "energies would not convert to double exactly\n", ph ? "S" : "P");
+            return 1;
+        }
+    }
+    if (o->vref)
+        for (int i = 0; i < D.ncm; i++) {
+            const bool sph = i >= D.ncell;
+            const int lo = sph ? D.vsmin : D.vmin, hi = sph ? D.vsmax : D.vmax;
+            if (o->vref[i] < lo || o->vref[i] > hi) {
+                fprintf(stderr, "mceik_mcmc_prior_enable: vref[%d] = %d outside the box [%d, %d]\n", i, o->vref[i], lo, hi);
+                return 1;
+            }
+        }
+    if (s->post && mcmc_post_count(s->post) > 0) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    const int nch = D.nchains;
+    if (!s->P.dE) {                    // all three or none: a failed enable leaves the sampler as it was
+        long long *dE = nullptr;
+        unsigned long long *pen = nullptr;
+        int *vref = nullptr;
+        if (dalloc(s, &dE, 2 * (size_t)nch) || dalloc(s, &pen, 2 * (size_t)nch * D.nphase) || dalloc(s, &vref, D.ncm))
+            return -1;
+        s->P.dE = dE;
+        s->d_pen = pen;
+        s->d_vref = vref;
+    }
+    HIPCHK(hipMemset(s->P.dE, 0, 2 * (size_t)nch * 8));
+    if (o->vref) HIPCHK(hipMemcpy(s->d_vref, o->vref, (size_t)D.ncm * sizeof(int), hipMemcpyHostToDevice));
+    s->prior_vref = o->vref != nullptr;
+    s->P.vref = o->vref ? s->d_vref : nullptr;
+    s->P.ws0 = o->w_smooth[0]; s->P.ws1 = o->w_smooth[1];
+    s->P.wd0 = o->w_damp[0]; s->P.wd1 = o->w_damp[1];
+    s->prior_on = true;
+    return pipes_refresh(s);
+}
+
+extern "C" int mceik_mcmc_prior_disable(mceik_mcmc *s)
+{
+    if (!s) return 1;
+    if (!s->prior_on) return 0;
+    if (s->post && mcmc_post_count(s->post) > 0) return 1;
+    s->prior_on = false;               // host state only: queued steps keep the kernels they were queued with
+    return 0;
+}
+
+extern "C" int mceik_mcmc_prior_get(mceik_mcmc *s, mceik_prior_opts *o, int *vref)
+{
+    if (!s || !s->prior_on) return 1;
+    if (o) {
+        o->w_smooth[0] = s->P.ws0; o->w_smooth[1] = s->P.ws1;
+        o->w_damp[0] = s->P.wd0; o->w_damp[1] = s->P.wd1;
+        o->vref = s->prior_vref ? vref : nullptr;
+    }
+    if (vref && s->prior_vref) {
+        DeviceScope dg(s->device);
+        HIPCHK(hipMemcpy(vref, s->d_vref, (size_t)s->D.ncm * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+extern "C" int mceik_mcmc_prior_energy(mceik_mcmc *s, long long *Es, long long *Ed)
+{
+    if (!s || !s->prior_on) return 1;
+    DeviceScope dg(s->device);
+    const size_t n = (size_t)s->D.nchains * s->D.nphase;
+    HIPCHK(hipMemsetAsync(s->d_pen, 0, 2 * n * 8, s->stream));
+    HIPCHK(prior_energy(s->D, s->B, s->P, s->d_pen, s->d_pen + n, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    if (Es) HIPCHK(hipMemcpy(Es, s->d_pen, n * 8, hipMemcpyDeviceToHost));
+    if (Ed) HIPCHK(hipMemcpy(Ed, s->d_pen + n, n * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int mceik_mcmc_prior_last(mceik_mcmc *s, long long *dE)
+{
+    if (!s || !s->prior_on || !dE) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    HIPCHK(hipMemcpy(dE, s->P.dE, 2 * (size_t)s->D.nchains * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+static int prior_grid_ok(int ncx, int ncy, int ncz)
+{
+    return ncx >= 1 && ncy >= 1 && ncz >= 1 && (long long)ncx * ncy * ncz <= INT_MAX;
+}
+
+// Largest minus smallest value of v (and vref) over n cells.
+static long long prior_span(const int *v, const int *vref, int n)
+{
+    long long lo = v[0], hi = v[0];
+    for (int i = 0; i < n; i++) {
+        lo = std::min<long long>(lo, v[i]);
+        hi = std::max<long long>(hi, v[i]);
+        if (vref) {
+            lo = std::min<long long>(lo, vref[i]);
+            hi = std::max<long long>(hi, vref[i]);
+        }
+    }
+    return hi - lo;
+}
+
+extern "C" int mceik_prior_energy(int ncx, int ncy, int ncz, const int *v, const int *vref, long long *Es,
+                                  long long *Ed)
+{
+    if (!prior_grid_ok(ncx, ncy, ncz) || !v) return 1;
+    const int n = ncx * ncy * ncz;
+    if (!prior_fits(n, prior_span(v, vref, n))) return 1;
+    long long es = 0, ed = 0;
+    for (int i = 0; i < n; i++) prior_energy_cell(ncx, ncy, ncz, i, v, vref, &es, &ed);
+    if (Es) *Es = es;
+    if (Ed) *Ed = ed;
+    return 0;
+}
+
+extern "C" int mceik_prior_delta(int ncx, int ncy, int ncz, const int *v, const int *vref, int cell, int radius,
+                                 int amp, long long *dEs, long long *dEd)
+{
+    if (!prior_grid_ok(ncx, ncy, ncz) || !v || cell < 0 || cell >= ncx * ncy * ncz || radius < 0 ||
+        radius > MCEIK_BLOCK_RMAX || amp == 0 || amp == INT_MIN)
+        return 1;
+    const int n = ncx * ncy * ncz;
+    if (!prior_fits(n, prior_span(v, vref, n) + 2LL * (amp < 0 ? -(long long)amp : amp))) return 1;
+    const int cx = cell % ncx, cy = (cell / ncx) % ncy, cz = cell / (ncx * ncy);
+    const int m = 2 * radius + 2;
+    long long es = 0, ed = 0;
+    for (int k = 0; k < m * m * m; k++) prior_delta_cell(ncx, ncy, ncz, cx, cy, cz, radius, amp, k, v, vref, &es, &ed);
+    if (dEs) *dEs = es;
+    if (dEd) *dEd = ed;
+    return 0;
 }
 
 int mcmc_post_ctx(mceik_mcmc *s, McmcPostCtx *out)
@@ -349,7 +497,7 @@ extern "C" int mceik_mcmc_get_info(mceik_mcmc *s, mceik_mcmc_info *info)
     DeviceScope dg(s->device);
     memset(info, 0, sizeof(*info));
     info->npipe = s->npipe;
-    info->multi_step = s->persist && !s->block_on ? 1 : 0;   // block proposals step per launch
+    info->multi_step = s->persist && !s->block_on && !s->prior_on ? 1 : 0;   // block proposals and the prior step per launch
     info->nphase = s->D.nphase;
     info->masked_s = s->masked_s;
     FsmLaunch L;

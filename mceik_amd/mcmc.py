@@ -7,6 +7,7 @@ L2 misfit with analytic origin time -> Metropolis).  Multi-GPU runs shard the
 global chain ids over ranks (`shard`), one process per GPU.
 """
 import ctypes as C
+import hashlib
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -360,6 +361,64 @@ def block_footprint(p, cell, radius, amp):
     return cells[:cnt].copy(), dv[:cnt].copy()
 
 
+def _prior_model(grid, a, name):
+    a = np.ascontiguousarray(a, dtype=np.int32).ravel()
+    if a.size != int(grid.ncx) * int(grid.ncy) * int(grid.ncz):
+        raise ValueError(f"{name}: one model of ncx * ncy * ncz cells")
+    return a
+
+
+def prior_energy(grid, v, vref=None):
+    """(Es, Ed) of one ncx x ncy x ncz model `v` of `grid` (a Problem, or
+    anything with ncx, ncy, ncz), cells x fastest (mceik_prior_energy; host
+    only): the roughness sum of (v_i - v_j)^2 over face-adjacent pairs and the
+    damping sum of (v_i - vref_i)^2 (0 without `vref`), exact integers."""
+    v = _prior_model(grid, v, "v")
+    r = None if vref is None else _prior_model(grid, vref, "vref")
+    es, ed = C.c_longlong(0), C.c_longlong(0)
+    rc = _lib.lib().mceik_prior_energy(int(grid.ncx), int(grid.ncy), int(grid.ncz), v.ctypes.data_as(C.c_void_p),
+                                       None if r is None else r.ctypes.data_as(C.c_void_p), C.byref(es), C.byref(ed))
+    if rc != 0:
+        raise ValueError("prior_energy: a grid of at least one cell whose 3 ncell span^2 stays below 2^53")
+    return es.value, ed.value
+
+
+def prior_delta(grid, v, cell, radius, amp, vref=None):
+    """(dEs, dEd): what `prior_energy` changes by when the block footprint
+    (`block_footprint`) of signed amplitude `amp` and radius `radius` centred
+    on `cell` is added to `v` (mceik_prior_delta; host only, the arithmetic of
+    the sampler's fold kernel)."""
+    v = _prior_model(grid, v, "v")
+    r = None if vref is None else _prior_model(grid, vref, "vref")
+    es, ed = C.c_longlong(0), C.c_longlong(0)
+    rc = _lib.lib().mceik_prior_delta(int(grid.ncx), int(grid.ncy), int(grid.ncz), v.ctypes.data_as(C.c_void_p),
+                                      None if r is None else r.ctypes.data_as(C.c_void_p), int(cell), int(radius),
+                                      int(amp), C.byref(es), C.byref(ed))
+    if rc != 0:
+        raise ValueError("prior_delta: cell inside the model, radius in [0, 8], amp != 0, 3 ncell span^2 < 2^53")
+    return es.value, ed.value
+
+
+def prior_weight(sigma):
+    """w = 1 / (2 sigma^2) per phase from a sigma in m/s: a scalar (both
+    phases) or a (P, S) pair; None is weight 0."""
+    if sigma is None:
+        return (0.0, 0.0)
+    pair = tuple(sigma) if np.ndim(sigma) else (sigma, sigma)
+    if len(pair) != 2:
+        raise ValueError("a sigma is a scalar or a (P, S) pair")
+    out = []
+    for s in pair:
+        if s is None:
+            out.append(0.0)
+            continue
+        s = float(s)
+        if not (s > 0.0 and np.isfinite(s)):
+            raise ValueError("a sigma is positive and finite (None: weight 0)")
+        out.append(1.0 / (2.0 * s * s))
+    return tuple(out)
+
+
 class Sampler:
     """One GPU's chains (include/mceik.h handle)."""
 
@@ -396,6 +455,7 @@ class Sampler:
         self._temper_base = None        # (attempts, accepts) of a restored checkpoint: added to the device counters
         self._block = None              # (rmin, rmax) while block proposals are enabled
         self._block_base = None         # (attempts, accepts) of a restored checkpoint, as _temper_base
+        self._prior = None              # (w_smooth, w_damp, vref digest) while the prior is enabled
 
     @property
     def model_shape(self):
@@ -492,6 +552,8 @@ class Sampler:
         if self._block is not None:      # the radii decide what the chains propose; the counters ride along
             att, acc = self.block_stats()
             ck["block"] = {"rmin": self._block[0], "rmax": self._block[1], "attempts": att, "accepts": acc}
+        if self._prior is not None:      # the weights and the reference model decide what the chains sample
+            ck["prior"] = {"w_smooth": self._prior[0], "w_damp": self._prior[1], "vref_sha256": self._prior[2]}
         return ck
 
     def restore(self, ck, recompute_logl=False):
@@ -507,6 +569,10 @@ class Sampler:
         bk = ck.get("block")             # likewise: a checkpoint without the entry restores anywhere
         if bk is not None and (self._block is None or (int(bk["rmin"]), int(bk["rmax"])) != self._block):
             raise ValueError("the checkpoint was taken with other block-proposal radii")
+        pk = ck.get("prior")             # likewise
+        if pk is not None and (self._prior is None or
+                               (tuple(pk["w_smooth"]), tuple(pk["w_damp"]), pk["vref_sha256"]) != self._prior):
+            raise ValueError("the checkpoint was taken with other prior weights or another reference model")
         v = np.ascontiguousarray(ck["v"], dtype=np.int32)
         assert v.shape == self.model_shape
         logl = None if recompute_logl else np.ascontiguousarray(ck["logl"], dtype=np.float64)
@@ -696,6 +762,67 @@ class Sampler:
         if reset:
             self._block_base = None
         return att, acc
+
+    # --- smoothness / reference-model prior (include/mceik.h mceik_mcmc_prior_*) ---
+    def prior_enable(self, sigma_smooth=None, sigma_damp=None, vref=None):
+        """Turn the smoothness and reference-model prior on: log prior =
+        -(ws Es + wd Ed) per phase model beside the uniform box, Es the sum of
+        (v_i - v_j)^2 over face-adjacent cells, Ed the sum of (v_i - vref_i)^2
+        (`prior_energy`), w = 1 / (2 sigma^2).  Sigmas in m/s: a scalar or a
+        (P, S) pair, None = weight 0.  `vref`: one model shaped like a chain's
+        (model_shape[1:]), shared by the chains; damping needs it.  Every step
+        is then one launch (`info()["multi_step"]` is False until
+        `prior_disable`)."""
+        ws, wd = prior_weight(sigma_smooth), prior_weight(sigma_damp)
+        if vref is None and any(wd):
+            raise ValueError("prior_enable: sigma_damp needs a reference model vref")
+        o = _lib.PriorOpts()
+        o.w_smooth[0], o.w_smooth[1] = ws
+        o.w_damp[0], o.w_damp[1] = wd
+        r, digest = None, None
+        if vref is not None:
+            r = np.ascontiguousarray(vref, dtype=np.int32)
+            if r.shape != self.model_shape[1:]:
+                raise ValueError(f"prior_enable: vref shaped {self.model_shape[1:]}, not {r.shape}")
+            o.vref = r.ctypes.data
+            digest = hashlib.sha256(r.tobytes()).hexdigest()
+        rc = self._L.mceik_mcmc_prior_enable(self._h, C.byref(o))
+        if rc != 0:
+            raise (ValueError if rc == 1 else RuntimeError)(
+                f"mceik_mcmc_prior_enable failed ({rc}): finite weights >= 0, vref inside the box, 3 ncell (hi - lo + "
+                "2 dvmax)^2 < 2^53, and no states in an enabled posterior")
+        self._prior = (ws, wd, digest)
+
+    def prior_disable(self):
+        rc = self._L.mceik_mcmc_prior_disable(self._h)
+        if rc != 0:
+            raise (ValueError if rc == 1 else RuntimeError)(f"mceik_mcmc_prior_disable failed ({rc})")
+        self._prior = None
+
+    def _prior_on(self):
+        if self._prior is None:
+            raise RuntimeError("the prior is not enabled (Sampler.prior_enable)")
+        return self._prior
+
+    def prior_energy(self):
+        """(Es, Ed) int64 [nchains, nphase]: the energies of every chain's current
+        models, summed on the GPU."""
+        self._prior_on()
+        es, ed = (np.zeros((self.nchains, self.p.nphase), np.int64) for _ in range(2))
+        rc = self._L.mceik_mcmc_prior_energy(self._h, es.ctypes.data_as(C.c_void_p), ed.ctypes.data_as(C.c_void_p))
+        if rc != 0:
+            raise RuntimeError(f"mceik_mcmc_prior_energy failed ({rc})")
+        return es, ed
+
+    def prior_last(self):
+        """int64 [nchains, 2]: (dEs, dEd) of every chain's proposal of the last
+        step, accepted or not; zeros for a proposal outside the box."""
+        self._prior_on()
+        de = np.zeros((self.nchains, 2), np.int64)
+        rc = self._L.mceik_mcmc_prior_last(self._h, de.ctypes.data_as(C.c_void_p))
+        if rc != 0:
+            raise RuntimeError(f"mceik_mcmc_prior_last failed ({rc})")
+        return de
 
     def fsm_stats(self, reset=False):
         """(FSM kernel ms from hipEvents, launches, executed iterations summed over
