@@ -202,6 +202,14 @@ int mceik_fsm_step_z(const mceik_fsm_batch *b);
 const char *mceik_fsm_kernel_name(const mceik_fsm_batch *b);
 size_t mceik_fsm_lds_bytes(const mceik_fsm_batch *b);
 
+/* 0 when mceik_fsm_batch_solve accepts the batch's geometry, else non-zero
+ * with the reason on stderr: the checks the solve makes before it looks at the
+ * workspace (axes of 2..4096 nodes, a field below 2 GiB, the LDS block tables,
+ * the held stream's clocks, and for slow_mode 1 a refinement whose node -> cell
+ * multiply is exact on its axis: every nr <= 274).  Host-side, no GPU needed;
+ * mceik_mcmc_init makes the same check. */
+int mceik_fsm_check(const mceik_fsm_batch *b);
+
 /* Algorithmic HBM bytes of one node visit in one sweep (roofline accounting). */
 double mceik_fsm_bytes_per_node_sweep(const mceik_fsm_batch *b);
 

@@ -59,7 +59,10 @@ void fill_launch(FsmLaunch &L, const mceik_fsm_batch *b)
     L.skip = b->skip;
     L.solve_count = b->solve_count;
     L.nphase = b->nphase > 0 ? b->nphase : 1;
-    // LDS cell cache when every z-block's cells fit (2 x 2 x 8 at nref = 4, kb = 4)
+    // LDS cell cache when every z-block's cells fit: ccb = the most cells a z-block of a tile touches
+    // (2 x 2 x 8 at nref = 4, kb = 4; 4 x 4 x 11 at nref = 3; 8 x 8 x 32 at nref = 1, which does not
+    // fit and runs uncached).  Sized here with true divisions, indexed by the kernels with the magic
+    // multiply: mceik_fsm_check refuses the refinements at which the two differ (nr >= 275)
     {
         auto span = [](int a, int e, int nr) { return e / nr - a / nr + 1; };
         int mx = 0, my = 0, mz = 0;
@@ -235,8 +238,28 @@ extern "C" int mceik_fsm_batch_solve(const mceik_fsm_batch *b, void *workspace, 
     return fsm_batch_solve_impl(b, workspace, workspace_bytes, stream, nullptr);
 }
 
-int fsm_batch_solve_impl(const mceik_fsm_batch *b, void *workspace, size_t workspace_bytes, void *stream,
-                         const McmcExt *ext)
+// The kernels' node -> cell map, (node * ceil(2^20 / nr)) >> 20 in unsigned
+// 32-bit arithmetic (FsmLaunch.magic_r*), against node / nr for every node of
+// an axis of n <= 4096 nodes (the product stays below 2^32).  With
+// m = ceil(2^20 / nr), e = m nr - 2^20 and node = q nr + r the product is
+// q 2^20 + (q e + r m), so the map is exact iff q e + r m < 2^20; the term
+// grows with q and with r, so the axis' last node and the last node of its
+// last whole cell decide.  (Exact for every n <= 4096 up to nr = 274; the
+// first miss is nr = 275 at node 3849.)
+static bool cell_map_exact(int n, int nr)
+{
+    const uint64_t m = ((1u << 20) + (uint64_t)nr - 1) / nr, e = m * nr - (1u << 20);
+    const int last = n - 1, whole = n / nr * nr - 1;
+    for (int node : {last, whole}) {
+        if (node < 0) continue;
+        if ((uint64_t)(node / nr) * e + (uint64_t)(node % nr) * m >= 1u << 20) return false;
+    }
+    return true;
+}
+
+// Everything mceik_fsm_batch_solve refuses before it looks at the workspace
+// (host only: no GPU call).
+extern "C" int mceik_fsm_check(const mceik_fsm_batch *b)
 {
     if (!b || b->nx < 2 || b->ny < 2 || b->nz < 2 || b->nx > 4096 || b->ny > 4096 || b->nz > 4096 ||
         b->nsrc < 1 ||
@@ -244,28 +267,41 @@ int fsm_batch_solve_impl(const mceik_fsm_batch *b, void *workspace, size_t works
         fprintf(stderr, "mceik_fsm_batch_solve: invalid batch description\n");
         return 1;
     }
-    if (b->slow_mode == 1 && b->precision != 32 && b->precision != 64) return 1;
-    WsLayout w = ws_layout(b);
-    {
-        FsmLaunch G;
-        fill_launch(G, b);
-        if (G.field_elems * (b->precision == 64 ? 8 : 4) >= (size_t)1 << 31) {
-            fprintf(stderr, "mceik_fsm_batch_solve: one travel-time field must stay below 2 GiB\n");
-            return 1;
-        }
-        if (fsm_launch_lds_bytes(G, b->precision == 64) > MCEIK_MAX_LDS) {
-            fprintf(stderr, "mceik_fsm_batch_solve: %d x %d x %d z-blocks exceed the LDS block tables\n", G.ntx, G.nty,
-                    G.nzk);
-            return 1;
-        }
-        // the held stream's 16-bit sweep clocks (fsm_hold.h hold_clock_bound)
-        const bool held = fsm_launch_kind(G, b->precision == 64) == 16 || fsm_compact_layout(G, 8);
-        const int infl = fsm_launch_kind(G, b->precision == 64) == 16 ? fsm16_geo(G).infl : G.infl;
-        if (held && hold_clock_bound(G.nblocks, infl) >= 65536) {
-            fprintf(stderr, "mceik_fsm_batch_solve: %d z-blocks overflow the held stream's 16-bit clocks\n", G.nblocks);
-            return 1;
-        }
+    FsmLaunch G;
+    fill_launch(G, b);
+    if (b->slow_mode == 1) {
+        const int n[3] = {G.nx, G.ny, G.nz}, nr[3] = {G.nrx, G.nry, G.nrz};
+        for (int a = 0; a < 3; a++)
+            if (!cell_map_exact(n[a], nr[a])) {
+                fprintf(stderr, "mceik_fsm_batch_solve: refinement %d on the %c axis of %d nodes: the sweep kernels' "
+                                "20-bit node -> cell multiply is not exact there\n", nr[a], "xyz"[a], n[a]);
+                return 1;
+            }
     }
+    if (G.field_elems * (b->precision == 64 ? 8 : 4) >= (size_t)1 << 31) {
+        fprintf(stderr, "mceik_fsm_batch_solve: one travel-time field must stay below 2 GiB\n");
+        return 1;
+    }
+    if (fsm_launch_lds_bytes(G, b->precision == 64) > MCEIK_MAX_LDS) {
+        fprintf(stderr, "mceik_fsm_batch_solve: %d x %d x %d z-blocks exceed the LDS block tables\n", G.ntx, G.nty,
+                G.nzk);
+        return 1;
+    }
+    // the held stream's 16-bit sweep clocks (fsm_hold.h hold_clock_bound)
+    const bool held = fsm_launch_kind(G, b->precision == 64) == 16 || fsm_compact_layout(G, 8);
+    const int infl = fsm_launch_kind(G, b->precision == 64) == 16 ? fsm16_geo(G).infl : G.infl;
+    if (held && hold_clock_bound(G.nblocks, infl) >= 65536) {
+        fprintf(stderr, "mceik_fsm_batch_solve: %d z-blocks overflow the held stream's 16-bit clocks\n", G.nblocks);
+        return 1;
+    }
+    return 0;
+}
+
+int fsm_batch_solve_impl(const mceik_fsm_batch *b, void *workspace, size_t workspace_bytes, void *stream,
+                         const McmcExt *ext)
+{
+    if (mceik_fsm_check(b)) return 1;
+    WsLayout w = ws_layout(b);
     if (!workspace || workspace_bytes < w.total) {
         fprintf(stderr, "mceik_fsm_batch_solve: workspace too small (%zu < %zu)\n", workspace_bytes, w.total);
         return 1;

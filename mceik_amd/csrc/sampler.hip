@@ -311,6 +311,20 @@ extern "C" int mceik_mcmc_init(const struct mceik_parms_struct *parms, const str
         fprintf(stderr, "mceik_mcmc_init: invalid options\n");
         return 1;
     }
+    {
+        // the forward solve's own geometry check (mceik_fsm_check: host only, it names the reason)
+        mceik_fsm_batch g;
+        memset(&g, 0, sizeof(g));
+        g.nx = o->nx; g.ny = o->ny; g.nz = o->nz;
+        g.precision = o->precision == 64 ? 64 : 32;
+        g.nmodel = o->nchains; g.nstat = st->nstat; g.nsrc = 1;
+        g.slow_mode = 1; g.nrx = parms->nrefx; g.nry = parms->nrefy; g.nrz = parms->nrefz;
+        g.fast_sqrt = parms->dx / (double)(nphase == 2 ? std::max(o->vmax, o->vsmax) : o->vmax) >= 1e-12 ? 1 : 0;
+        if (mceik_fsm_check(&g)) {
+            fprintf(stderr, "mceik_mcmc_init: the eikonal solver refuses this grid\n");
+            return 1;
+        }
+    }
     for (int e = 0; e < cat->nevents; e++)
         if (cat->obsPtr[e + 1] < cat->obsPtr[e]) {
             fprintf(stderr, "mceik_mcmc_init: obsPtr must be non-decreasing\n");
