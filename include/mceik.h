@@ -381,6 +381,86 @@ int mceik_prior_energy(int ncx, int ncy, int ncz, const int *v, const int *vref,
 int mceik_prior_delta(int ncx, int ncy, int ncz, const int *v, const int *vref, int cell, int radius, int amp,
                       long long *dEs, long long *dEd);
 
+/* ---- hypocentre moves (csrc/hypo.hip) --------------------
+ * Off by default; with it off nothing changes: every chain fits its picks at
+ * the catalogue's hypocentres snapped to their nearest nodes.  Enabled, every
+ * chain carries a position of its own per event, hyp[nchains][nev][3] = node
+ * indices (ix, iy, iz), 0-based, which start at the catalogue's nodes at the
+ * first enable and from then on stay per chain, also after disable.  Origin
+ * time stays marginalised analytically, as in every objfn.
+ *
+ * With every = K > 0 global step gs is a hypocentre step iff gs % K == K - 1.
+ * It replaces that step's velocity proposal: v and naccept do not change,
+ * mceik_mcmc_last's accept flags are 0, the kept-state and posterior rules
+ * apply with the step's new logL, a swap round of gs runs first.  Block
+ * proposals and the prior act on velocity steps only.  For chain c (global id
+ * g) and event e:
+ *   r = Philox4x32-10(counter {(uint32)gs, (uint32)(gs >> 32), 2, e}, key {g, seed})
+ *       (counter word 2: proposals 0, swaps 1)
+ *   d[a] = (int)(((uint64)r[a] * (2 dmax[a] + 1)) >> 32) - dmax[a],  a = 0, 1, 2
+ *   log u = det_log((r[3] + 0.5) / 2^32)
+ *   candidate = current + d; inside iff lo[a] <= candidate[a] <= hi[a] on every axis
+ * (a symmetric draw: no Hastings term).  One forward of the chain's current
+ * models extracts every station's time at each event's current and candidate
+ * node; obj_cur and obj_cand are the event's objfn (the sampler's L2 misfit
+ * with the analytic origin time, the same operations in the same order) at
+ * the two, every phase from that forward, and
+ *   accept iff inside and log u < obj_cur - obj_cand
+ *              (tempering: log u < beta * (obj_cur - obj_cand), one fp64
+ *               multiply; the uniform box is not tempered)
+ * per event: logL = -sum_e objfn_e and the events are independent given the
+ * model, so every event's move is an exact Metropolis step.  Then logL = 0;
+ * logL = logL - obj_sel[e] in event order (obj_sel: the accepted side's
+ * value), bitwise the logL of a full forward at the chain's models and new
+ * positions.  A tempering swap exchanges the two chains' positions with their
+ * models; its rule does not change (the box is the same for both replicas).
+ *
+ * While enabled every step is one launch of each kernel
+ * (mceik_mcmc_info.multi_step reports 0 until disable), and after every kept
+ * step (nburnIn / keepK) the cold chains' positions are added to exact
+ * integer moments per event: n states, sum[nev][3] of (x, y, z) and sq[nev][6]
+ * of (xx, yy, zz, xy, xz, yz) in nodes -- the location mean and covariance
+ * without stored states; pipes and ranks merge them by addition.
+ *
+ * enable refuses (1): NULL options, every < 0, a dmax < 0, lo > hi or a box
+ * outside the grid, a chain's current position outside the box, a sampler with
+ * tt_interp = 1, and an enabled posterior that holds states.  The other
+ * functions return 1 before the first enable.  A checkpoint is
+ * mceik_mcmc_checkpoint plus hypo_get and hypo_moments_get; a resume is
+ * hypo_set, then mceik_mcmc_restore with the saved logl (two models: with
+ * logl NULL, as every two-model resume, so that its forward makes the current
+ * tables of both models; it gives the saved logl), then hypo_moments_set.
+ * Positions are not part of the kept ring nor of mceik_mcmc_gather.
+ *
+ * Every function returns 0, 1 on invalid arguments or -1 on a device failure. */
+typedef struct mceik_hypo_opts { int every; int dmax[3]; int lo[3], hi[3]; } mceik_hypo_opts;
+/* Turns hypocentre moves on (or replaces the options).  Synchronises; resets
+ * the counters and the moments. */
+int mceik_mcmc_hypo_enable(mceik_mcmc *s, const mceik_hypo_opts *o);
+/* Later steps are velocity steps again; the positions stay, per chain. */
+int mceik_mcmc_hypo_disable(mceik_mcmc *s);
+/* The options in force (every = 0 after disable; o may be NULL) and the
+ * positions xyz [nchains][nev][3] (or NULL).  Synchronises. */
+int mceik_mcmc_hypo_get(mceik_mcmc *s, mceik_hypo_opts *o, int *xyz);
+/* Replaces the positions (inside the grid; inside the box while enabled); one
+ * full forward recomputes logL (2: a solve failed, as mceik_mcmc_restore).
+ * Synchronises. */
+int mceik_mcmc_hypo_set(mceik_mcmc *s, const int *xyz);
+/* attempts, accepts [nev]: moves tried and accepted per event over the chains
+ * (either may be NULL).  Synchronises. */
+int mceik_mcmc_hypo_stats(mceik_mcmc *s, long long *attempts, long long *accepts, int reset);
+/* The last hypocentre step: cand [nchains][nev][3] = current + d (also when
+ * outside), accept [nchains][nev], obj [nchains][nev][2] = objfn at the
+ * current, the candidate node (a candidate outside: at the current node).
+ * Any may be NULL.  Synchronises. */
+int mceik_mcmc_hypo_last(mceik_mcmc *s, int *cand, unsigned char *accept, double *obj);
+/* The moments: n, sum [nev][3], sq [nev][6] (get: any may be NULL). */
+int mceik_mcmc_hypo_moments_get(mceik_mcmc *s, long long *n, long long *sum, long long *sq);
+int mceik_mcmc_hypo_moments_set(mceik_mcmc *s, long long n, const long long *sum, const long long *sq);
+/* Host only (no GPU call): the draw of event e of global chain gchain at
+ * global step `step`: d[3] and log u (may be NULL). */
+int mceik_hypo_draw(uint32_t seed, uint32_t gchain, uint64_t step, int e, const int dmax[3], int d[3], double *logu);
+
 /* ---- multi-rank runs (one process per GPU; csrc/comm.hip) ---------------
  * The sampler's only collective is the checkpoint gather (SURVEY s.8e) over
  * RCCL (xGMI on one node).  Bootstrap as RCCL's: rank 0 calls

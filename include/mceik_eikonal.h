@@ -173,6 +173,11 @@ typedef struct mceik_fsm_batch {
                                    sweep, niter 0, ierr 0, its ttab row FLT_MAX (the unreached value).
                                    Refused together with u_out (a skipped solve has no field) */
     unsigned long long *solve_count; /* device counter += solves executed (not skipped), or NULL */
+    int ev_stride;              /* 0: every model samples its tables at the one list ev_node[nev] (and
+                                   ev_frac[nev][3]).  > 0: model m = solve / nstat of the batch samples at
+                                   ev_node[m * ev_stride + e] (fractions ev_frac[3 * (m * ev_stride + e) ..]):
+                                   a list of its own per model, rows ev_stride entries apart; ttab stays
+                                   [nmodel*nstat][nev] */
 } mceik_fsm_batch;
 
 /* The batched extension of SURVEY s.8b with plain arguments: nmodels x

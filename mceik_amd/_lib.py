@@ -26,7 +26,7 @@ class FsmBatch(C.Structure):
                 ("visit_stats", C.c_void_p), ("solve_order", C.c_void_p), ("solve_clock", C.c_void_p),
                 ("max_waves", C.c_int), ("traffic", C.c_void_p), ("step_z", C.c_int),
                 ("ev_frac", C.c_void_p), ("model_phase", C.c_void_p), ("nphase", C.c_int),
-                ("skip", C.c_void_p), ("solve_count", C.c_void_p)]
+                ("skip", C.c_void_p), ("solve_count", C.c_void_p), ("ev_stride", C.c_int)]
 
 
 class RelocateBatch(C.Structure):
@@ -114,6 +114,11 @@ class PriorOpts(C.Structure):
     _fields_ = [("w_smooth", C.c_double * 2), ("w_damp", C.c_double * 2), ("vref", C.c_void_p)]
 
 
+class HypoOpts(C.Structure):
+    """mceik_hypo_opts (include/mceik.h)."""
+    _fields_ = [("every", C.c_int), ("dmax", C.c_int * 3), ("lo", C.c_int * 3), ("hi", C.c_int * 3)]
+
+
 # every extern "C" symbol include/*.h declares
 EXPORTS = ("eikonal3d_serial_driver", "eikonal3d_serial_driver_sp", "eikonal3d_batch_solve", "eikonal3d_initialize", "eikonal3d_solve",
            "eikonal3d_finalize", "locate3d_gridsearch__double64", "locate3d_gridsearch__float64",
@@ -136,6 +141,9 @@ EXPORTS = ("eikonal3d_serial_driver", "eikonal3d_serial_driver_sp", "eikonal3d_b
            "mceik_block_footprint",
            "mceik_mcmc_prior_enable", "mceik_mcmc_prior_disable", "mceik_mcmc_prior_get", "mceik_mcmc_prior_energy",
            "mceik_mcmc_prior_last", "mceik_prior_energy", "mceik_prior_delta",
+           "mceik_mcmc_hypo_enable", "mceik_mcmc_hypo_disable", "mceik_mcmc_hypo_get", "mceik_mcmc_hypo_set",
+           "mceik_mcmc_hypo_stats", "mceik_mcmc_hypo_last", "mceik_mcmc_hypo_moments_get",
+           "mceik_mcmc_hypo_moments_set", "mceik_hypo_draw",
            "mceik_parms_defaults", "mceik_parms_set", "mceik_parms_read", "mceik_parms_args", "mceik_parms_write",
            "mceik_comm_available", "mceik_comm_unique_id", "mceik_comm_init", "mceik_comm_finalize", "mceik_mcmc_gather",
            "os_path_exists", "os_path_isdir", "os_path_isfile", "os_makedirs", "os_mkdir")
@@ -281,5 +289,24 @@ def lib():
     L.mceik_prior_energy.argtypes = [C.c_int] * 3 + [C.c_void_p] * 2 + [C.POINTER(C.c_longlong)] * 2
     L.mceik_prior_delta.restype = C.c_int
     L.mceik_prior_delta.argtypes = [C.c_int] * 3 + [C.c_void_p] * 2 + [C.c_int] * 3 + [C.POINTER(C.c_longlong)] * 2
+    L.mceik_mcmc_hypo_enable.restype = C.c_int
+    L.mceik_mcmc_hypo_enable.argtypes = [C.c_void_p, C.POINTER(HypoOpts)]
+    L.mceik_mcmc_hypo_disable.restype = C.c_int
+    L.mceik_mcmc_hypo_disable.argtypes = [C.c_void_p]
+    L.mceik_mcmc_hypo_get.restype = C.c_int
+    L.mceik_mcmc_hypo_get.argtypes = [C.c_void_p, C.POINTER(HypoOpts), C.c_void_p]
+    L.mceik_mcmc_hypo_set.restype = C.c_int
+    L.mceik_mcmc_hypo_set.argtypes = [C.c_void_p, C.c_void_p]
+    L.mceik_mcmc_hypo_stats.restype = C.c_int
+    L.mceik_mcmc_hypo_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.mceik_mcmc_hypo_last.restype = C.c_int
+    L.mceik_mcmc_hypo_last.argtypes = [C.c_void_p] * 4
+    L.mceik_mcmc_hypo_moments_get.restype = C.c_int
+    L.mceik_mcmc_hypo_moments_get.argtypes = [C.c_void_p, C.POINTER(C.c_longlong), C.c_void_p, C.c_void_p]
+    L.mceik_mcmc_hypo_moments_set.restype = C.c_int
+    L.mceik_mcmc_hypo_moments_set.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]
+    L.mceik_hypo_draw.restype = C.c_int
+    L.mceik_hypo_draw.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p,
+                                  C.POINTER(C.c_double)]
     _lib = L
     return L

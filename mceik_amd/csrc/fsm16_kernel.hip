@@ -1443,7 +1443,8 @@ __device__ __forceinline__ void fsm16_body(const FsmLaunch &L)
         TRAFU(S, 7, (FT ? 0u : (unsigned)(L.field_elems * 4)) + (L.ttab ? (unsigned)L.nev * (4u + 64u) : 0u));
         TRAF_FLUSH(L, S);
         if (L.ttab) {
-            for (int e = lane; e < L.nev; e += 64) L.ttab[(size_t)solve * L.nev + e] = event_time<float>(L, u, e);
+            const int er = event_row(L, solve);
+            for (int e = lane; e < L.nev; e += 64) L.ttab[(size_t)solve * L.nev + e] = event_time<float>(L, u, er + e);
         }
         if (MC) mc_finish(L, (int)solve, mk);
         __builtin_amdgcn_s_waitcnt(0);

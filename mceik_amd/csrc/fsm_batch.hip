@@ -55,6 +55,7 @@ void fill_launch(FsmLaunch &L, const mceik_fsm_batch *b)
     L.magic_ry = ((1u << 20) + L.nry - 1) / L.nry;
     L.magic_rz = ((1u << 20) + L.nrz - 1) / L.nrz;
     L.ev_node = b->ev_node; L.nev = b->nev; L.ttab = b->ttab; L.ev_frac = b->ev_frac;
+    L.ev_stride = b->ev_stride;
     L.model_phase = b->slow_mode == 1 ? b->model_phase : nullptr;
     L.skip = b->skip;
     L.solve_count = b->solve_count;
@@ -309,6 +310,12 @@ int fsm_batch_solve_impl(const mceik_fsm_batch *b, void *workspace, size_t works
     if (b->skip && b->u_out) {
         // a skipped solve never sweeps, so its u slot would hold stale workspace
         fprintf(stderr, "mceik_fsm_batch_solve: skip and u_out cannot be combined (a skipped solve has no field)\n");
+        return 1;
+    }
+    // per-model event lists: rows of at least nev entries, indexed in int
+    if (b->ev_stride < 0 || (b->ev_stride > 0 && (b->ev_stride < b->nev ||
+                                                  (long long)b->nmodel * b->ev_stride > 0x7fffffffLL))) {
+        fprintf(stderr, "mceik_fsm_batch_solve: ev_stride must be 0 or >= nev, with nmodel * ev_stride below 2^31\n");
         return 1;
     }
     hipStream_t st = (hipStream_t)stream;

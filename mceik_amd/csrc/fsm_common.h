@@ -72,6 +72,7 @@ struct FsmLaunch {
     unsigned mc_spin_limit;      // polls of a step-ready wait before the queue counts as broken
     int mc_step0, mc_nsteps;
     int mc_nburn, mc_keepk, mc_maxs, mc_nkept0;   // kept-state slots (mceik_mcmc_run's bookkeeping)
+    int ev_stride;               // > 0: model m = solve / nstat reads ev_node / ev_frac at m * ev_stride + e; 0: one list
 };
 #define MC_SYNC_WORDS(nchains) (8 + 8 * 32 + 2 * (nchains) + 1)
 

@@ -130,7 +130,9 @@ __device__ __forceinline__ size_t brick_index(const FsmLaunch &L, int x, int y, 
 // cell whose lowest corner is ev_node[e], with fractions ev_frac[3e..3e+2]:
 // x first, then y, then z, each lerp a + w*(b - a) in fp32 with every
 // operation rounded (no contraction) -- oracle/mceik_oracle.c
-// oracle_event_time restates it operation for operation.
+// oracle_event_time restates it operation for operation.  e indexes ev_node /
+// ev_frac: the event, plus the model's row offset when the models of the batch
+// have lists of their own (FsmLaunch.ev_stride; event_row).
 template <typename R>
 __device__ __forceinline__ float event_time(const FsmLaunch &L, const R *u, int e)
 {
@@ -150,6 +152,15 @@ __device__ __forceinline__ float event_time(const FsmLaunch &L, const R *u, int 
     const float b0 = __fadd_rn(a[0], __fmul_rn(wy, __fsub_rn(a[1], a[0])));
     const float b1 = __fadd_rn(a[2], __fmul_rn(wy, __fsub_rn(a[3], a[2])));
     return __fadd_rn(b0, __fmul_rn(wz, __fsub_rn(b1, b0)));
+}
+
+// Offset of a solve's event list in ev_node / ev_frac: its model's row when
+// the batch has per-model lists (ev_stride > 0), else 0.  Called once per
+// solve, after the sweeps (one division there instead of a model index held
+// across them).
+__device__ __forceinline__ int event_row(const FsmLaunch &L, unsigned solve)
+{
+    return (int)(solve / (unsigned)L.nstat) * L.ev_stride;
 }
 
 // A skipped solve (mceik_fsm_batch.skip: the station has no picks of the

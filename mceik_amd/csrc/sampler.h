@@ -10,6 +10,7 @@
 #include "../../include/mceik.h"
 #include "block.h"
 #include "fsm_common.h"
+#include "hypo.h"
 #include "posterior.h"
 #include "prior.h"
 
@@ -17,14 +18,16 @@
 #define MCEIK_MAX_PIPES 4
 #define MCEIK_ITERS_N (6 + MCEIK_TRAFFIC_N)   // d_iters: iterations, 4 visit statistics, solves, traffic
 
-// A pipe: a part of the chains stepped on a stream of its own.  D, B, P and fb
-// are views of the sampler's D, B, P and fb restricted to the pipe's chains;
+// A pipe: a part of the chains stepped on a stream of its own.  D, B, P, H, fb
+// and fb_hyp are views of the sampler's restricted to the pipe's chains;
 // pipes_refresh alone writes them.
 struct Pipe {
     McmcDev D;
     BlockDev B;
     PriorDev P;
+    HypoDev H;
     mceik_fsm_batch fb;
+    mceik_fsm_batch fb_hyp;            // a hypocentre step's batch (every model of the pipe's chains)
     void *ws;                          // the pipe's workspace: a part of the sampler's ws, ws itself, or its own
     size_t ws_bytes;
     bool ws_own;                       // ws was allocated for the pipe
@@ -93,6 +96,20 @@ struct mceik_mcmc {
     bool prior_vref;                   // a reference model is loaded (P.vref == d_vref)
     int *d_vref;                       // [nphase][ncell]
     unsigned long long *d_pen;         // [2][nchains * nphase] Es, Ed of mceik_mcmc_prior_energy
+    // Hypocentre moves (hypo.hip); off by default.  H.hyp is
+    // null until the first enable, which starts every chain at the catalogue's
+    // snapped nodes (ev_host) and switches fb / fb_all to per-chain event lists
+    // (ev_stride); the positions then stay per chain, also after disable.
+    // While on, every step takes the per-step branch; global step gs is a
+    // hypocentre step iff gs % hypo_every == hypo_every - 1.
+    bool hypo_on;
+    int hypo_every;
+    HypoDev H;
+    mceik_fsm_batch fb_hyp;            // fb_all on slow_cur with the [current | candidate] lists, tables into H.ttab2
+    std::vector<int> ev_host;          // [nev] the catalogue's snapped nodes
+    int tt_interp;                     // trilinear mode (hypocentre moves are refused)
+    unsigned long long *d_hcnt;        // [2][nev] attempts, accepts
+    long long hyp_n;                   // states in the moments (cold chains x kept steps)
     hipStream_t stream;
     void *ws;
     size_t ws_bytes;

@@ -3,8 +3,8 @@
 // time, the pipes, the forward launch and the step loop.
 //
 // Host orchestration only.  The numerics live in fsm_kernel.hip,
-// fsm16_kernel.hip, mcmc_kernels.hip, temper.hip, block.hip, prior.hip and
-// posterior.hip.
+// fsm16_kernel.hip, mcmc_kernels.hip, temper.hip, block.hip, prior.hip,
+// hypo.hip and posterior.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -60,8 +60,10 @@ int fold_launch(mceik_mcmc *s, long long k)
 // sampler's, which one pipe steps on.
 static hipStream_t pipe_stream(const mceik_mcmc *s, int k) { return s->npipe > 1 ? s->pipe[k].st : s->stream; }
 
-// The FSM launch of pipe k's batch on its stream.
-static int mcmc_forward(mceik_mcmc *s, bool timed, int k, const McmcExt *ext = nullptr)
+// The FSM launch of pipe k's batch on its stream: the step batch, or with hyp
+// the hypocentre step's (every model of the pipe's chains at [current |
+// candidate]).
+static int mcmc_forward(mceik_mcmc *s, bool timed, int k, const McmcExt *ext = nullptr, bool hyp = false)
 {
     Pipe &p = s->pipe[k];
     const hipStream_t st = pipe_stream(s, k);
@@ -80,13 +82,13 @@ static int mcmc_forward(mceik_mcmc *s, bool timed, int k, const McmcExt *ext = n
         }
         HIPCHK(hipEventRecord(s->ev[2 * r], st));
     }
-    if (fsm_batch_solve_impl(&p.fb, p.ws, p.ws_bytes, st, ext)) return -1;
+    if (fsm_batch_solve_impl(hyp ? &p.fb_hyp : &p.fb, p.ws, p.ws_bytes, st, ext)) return -1;
     s->last_ttab = s->fb.ttab;
     if (timed) {
         HIPCHK(hipEventRecord(s->ev[2 * r + 1], st));
         s->nlaunch++;
     }
-    if (s->d_order && s->npipe == 1) {  // the next launch pulls this launch's longest solves first (one pipe only)
+    if (s->d_order && s->npipe == 1 && !hyp) {  // the next launch pulls this launch's longest solves first (one pipe only)
         HIPCHK(mcmc_lpt_order(s->d_clock, p.fb.nmodel * p.fb.nstat, s->d_order, st));
         // the batch the next launch uses, and the sampler's, which pipes_refresh derives it from
         p.fb.solve_order = s->fb.solve_order = s->d_order;
@@ -163,6 +165,37 @@ static PriorDev dev_view(const PriorDev &P, int off)
     return V;
 }
 
+// The same view of the hypocentre state's per-chain arrays (the counters and moments are the sampler's).
+static HypoDev dev_view(const HypoDev &H, const McmcDev &D, int off)
+{
+    HypoDev V = H;
+    if (!H.hyp) return V;
+    const size_t o = (size_t)off, oe = o * D.nev;
+    V.hyp += 3 * oe; V.ev1 += oe; V.cand += 3 * oe; V.acc += oe; V.obj += 2 * oe; V.logu += oe;
+    if (V.evall) V.evall += oe * D.nphase;
+    V.ev2 += 2 * oe * D.nphase;
+    V.ttab2 += 2 * oe * D.nphase * D.nstat;
+    return V;
+}
+
+// Chains [off, off + n) of the hypocentre step's batch: nphase models per
+// chain.  It runs in the workspace of the pipe's step batch sb, so it keeps at
+// most that batch's resident waves (the workspace grows with the waves only).
+static mceik_fsm_batch hyp_batch_view(const mceik_fsm_batch &b, const mceik_fsm_batch &sb, int off, int n, size_t ncm,
+                                      int nphase)
+{
+    mceik_fsm_batch V = b;
+    const size_t om = (size_t)off * nphase, os = om * b.nstat;
+    V.nmodel = n * nphase;
+    V.slow = (const float *)b.slow + (size_t)off * ncm;
+    V.ev_node = b.ev_node + om * b.ev_stride;
+    V.ttab = b.ttab + os * b.nev;
+    V.niter = b.niter + os;
+    V.ierr = b.ierr + os;
+    V.max_waves = ws_layout(&sb).nwaves;
+    return V;
+}
+
 static mceik_fsm_batch batch_view(const mceik_fsm_batch &b, int off, int n, size_t ncm)
 {
     mceik_fsm_batch V = b;
@@ -171,6 +204,7 @@ static mceik_fsm_batch batch_view(const mceik_fsm_batch &b, int off, int n, size
     V.slow = (const float *)b.slow + o * ncm;       // a chain's models are ncm = nphase * ncell floats
     if (V.model_phase) V.model_phase = b.model_phase + o;
     V.ttab = b.ttab + os * b.nev;
+    if (b.ev_stride) V.ev_node = b.ev_node + o * b.ev_stride;     // per-chain event lists (hypocentre moves)
     V.niter = b.niter + os;
     V.ierr = b.ierr + os;
     V.solve_order = nullptr;
@@ -191,6 +225,8 @@ int pipes_refresh(mceik_mcmc *s)
         p.B = dev_view(s->B, lo);
         p.P = dev_view(s->P, lo);
         p.fb = batch_view(s->fb, lo, n, (size_t)s->D.ncm);
+        p.H = dev_view(s->H, s->D, lo);
+        if (s->H.hyp) p.fb_hyp = hyp_batch_view(s->fb_hyp, p.fb, lo, n, (size_t)s->D.ncm, s->D.nphase);
     }
     // the longest-first order covers the whole batch: one pipe's (mcmc_forward)
     if (np == 1) s->pipe[0].fb.solve_order = s->fb.solve_order;
@@ -393,6 +429,7 @@ extern "C" int mceik_mcmc_init(const struct mceik_parms_struct *parms, const str
     s->step = 0;
     s->nkept = 0;
     s->masked_s = nphase == 1 ? nsused : 0;
+    s->tt_interp = o->tt_interp ? 1 : 0;
     s->nburn = parms->mcparms.nburnIn;
     s->keepk = parms->mcparms.keepK > 0 ? parms->mcparms.keepK : 1;
     s->niter_total = parms->mcparms.niter;
@@ -432,6 +469,7 @@ extern "C" int mceik_mcmc_init(const struct mceik_parms_struct *parms, const str
         }
         ev[e] = (iz * o->ny + iy) * o->nx + ix;
     }
+    s->ev_host = ev;
     std::vector<int> ostat(nobs > 0 ? nobs : 1), omask(nobs > 0 ? nobs : 1), ophase(nobs > 0 ? nobs : 1);
     std::vector<double> tcorr(nobs > 0 ? nobs : 1);
     for (int j = 0; j < nobs; j++) {
@@ -635,9 +673,24 @@ static bool swap_step(const mceik_mcmc *s, long long gs)
 
 int temper_round(mceik_mcmc *s, int parity)
 {
+    // (per-chain hypocentres travel with their models, enabled or not)
     HIPCHK(temper_swap_round(s->D, s->ntemps, parity, (uint64_t)s->step, s->d_tflag, s->d_tcnt,
-                             s->d_tcnt + s->D.nchains, s->stream));
+                             s->d_tcnt + s->D.nchains, s->stream, s->H.hyp ? &s->H : nullptr));
     return 0;
+}
+
+// Global step gs moves hypocentres instead of proposing a velocity.
+static bool hypo_step(const mceik_mcmc *s, long long gs)
+{
+    return s->hypo_on && s->hypo_every > 0 && gs % s->hypo_every == s->hypo_every - 1;
+}
+
+// The moments see the cold chains only, as the posterior does (post_add).
+static hipError_t hypo_add(mceik_mcmc *s, const McmcDev &V, const HypoDev &H, int off, hipStream_t st)
+{
+    const int G = temper_cold(s);
+    if (off >= G) return hipSuccess;
+    return hypo_moments(V, H, std::min(V.nchains, G - off), st);
 }
 
 // Steps of one call.  Returns -1 on a HIP failure; the caller joins the pipes
@@ -647,8 +700,9 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
 {
     // block proposals: the multi-step kernel's epilogue is single-cell, so a
     // sampler built for multi-step launches (one pipe) steps per launch; the
-    // prior's fold sits between a step's proposal and its forward, likewise
-    if (s->persist && !s->block_on && !s->prior_on) {
+    // prior's fold sits between a step's proposal and its forward, likewise;
+    // a hypocentre step has kernels and a batch of its own
+    if (s->persist && !s->block_on && !s->prior_on && !s->hypo_on) {
         // the first step's proposals here, then up to MCEIK_MC_CHUNK steps per
         // FSM launch (the kernel accepts, keeps and proposes the rest)
         for (int done = 0; done < nsteps;) {
@@ -683,6 +737,7 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
         uint64_t step = (uint64_t)s->step;
         int slot = -1;
         const bool post = s->post && kept_step(s, s->step);
+        const bool hstep = hypo_step(s, s->step), hmom = s->hypo_on && kept_step(s, s->step);
         if (s->max_samples && s->step >= s->nburn && (s->step - s->nburn) % s->keepk == 0) {
             slot = s->nkept % s->max_samples;
             s->nkept++;
@@ -703,14 +758,22 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
         for (int k = 0; k < np; k++) {
             const Pipe &p = s->pipe[k];
             const hipStream_t st = pipe_stream(s, k);
-            HIPCHK(blk ? block_propose(p.D, p.B, step, st) : mcmc_propose(p.D, step, st));
-            if (s->prior_on) HIPCHK(prior_fold(p.D, p.B, p.P, blk, st));
-            if (mcmc_forward(s, true, k)) return -1;
-            HIPCHK(blk ? block_accept(p.D, p.B, slot, st) : mcmc_accept(p.D, slot, st));
+            if (hstep) {            // every event of every chain moves on one forward of the current models
+                HIPCHK(hypo_propose(p.D, p.H, step, st));
+                if (mcmc_forward(s, true, k, nullptr, true)) return -1;
+                HIPCHK(hypo_accept(p.D, p.H, slot, st));
+            } else {
+                HIPCHK(blk ? block_propose(p.D, p.B, step, st) : mcmc_propose(p.D, step, st));
+                if (s->prior_on) HIPCHK(prior_fold(p.D, p.B, p.P, blk, st));
+                if (mcmc_forward(s, true, k)) return -1;
+                HIPCHK(blk ? block_accept(p.D, p.B, slot, st) : mcmc_accept(p.D, slot, st));
+            }
             if (post)               // the pipe's rows of the accumulators, offset like its keep_v (dev_view)
                 HIPCHK(post_add(s, p.D, p.D.chain_offset - s->D.chain_offset, st));
+            if (hmom) HIPCHK(hypo_add(s, p.D, p.H, p.D.chain_offset - s->D.chain_offset, st));
         }
         if (post) mcmc_post_counted(s->post);
+        if (hmom) s->hyp_n += temper_cold(s);
         if (s->report) clock_report(s, "step");
         s->step++;
     }

@@ -1,7 +1,7 @@
 // sampler_api.hip -- the sampler's accessors of the C-ABI (include/mceik.h:
 // sync, state, checkpoint / restore, kept samples, info, FSM statistics) and
-// its parallel-tempering, block-proposal and prior entry points.  The sampler
-// itself is sampler.hip.
+// its parallel-tempering, block-proposal, prior and hypocentre entry points.
+// The sampler itself is sampler.hip.
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <limits.h>
@@ -319,6 +319,205 @@ extern "C" int mceik_prior_delta(int ncx, int ncy, int ncz, const int *v, const 
     return 0;
 }
 
+// ---------------------------------------------------------------------------
+// hypocentre moves (include/mceik.h mceik_mcmc_hypo_*)
+
+static int forward_logl(mceik_mcmc *s, const char *who);
+
+static bool hypo_in(const int *q, const int *lo, const int *hi)
+{
+    return q[0] >= lo[0] && q[0] <= hi[0] && q[1] >= lo[1] && q[1] <= hi[1] && q[2] >= lo[2] && q[2] <= hi[2];
+}
+
+// Every position of xyz [n][3] inside [lo, hi]; names the first that is not.
+static bool hypo_all_in(const char *who, const int *xyz, size_t n, int nev, const int *lo, const int *hi)
+{
+    for (size_t i = 0; i < n; i++)
+        if (!hypo_in(xyz + 3 * i, lo, hi)) {
+            fprintf(stderr, "%s: chain %zu, event %zu at node (%d, %d, %d) outside [%d, %d] x [%d, %d] x [%d, %d]\n", who,
+                    i / nev, i % nev, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], lo[0], hi[0], lo[1], hi[1], lo[2], hi[2]);
+            return false;
+        }
+    return true;
+}
+
+extern "C" int mceik_mcmc_hypo_enable(mceik_mcmc *s, const mceik_hypo_opts *o)
+{
+    if (!s || !o || o->every < 0) return 1;
+    const McmcDev &D = s->D;
+    const int n[3] = {s->fb.nx, s->fb.ny, s->fb.nz};
+    for (int a = 0; a < 3; a++)
+        if (o->dmax[a] < 0 || o->dmax[a] > 0x3fffffff || o->lo[a] > o->hi[a] || o->lo[a] < 0 || o->hi[a] >= n[a]) return 1;
+    if (s->tt_interp) {
+        fprintf(stderr, "mceik_mcmc_hypo_enable: hypocentres move by whole nodes; not with tt_interp = 1\n");
+        return 1;
+    }
+    if (s->post && mcmc_post_count(s->post) > 0) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    const int nch = D.nchains, nev = D.nev, nph = D.nphase;
+    const size_t ne = (size_t)nch * nev;
+    // the chains' positions: the catalogue's snapped nodes before the first enable
+    std::vector<int> xyz(ne * 3);
+    if (s->H.hyp) {
+        HIPCHK(hipMemcpy(xyz.data(), s->H.hyp, xyz.size() * sizeof(int), hipMemcpyDeviceToHost));
+    } else {
+        for (size_t i = 0; i < ne; i++) {
+            const int node = s->ev_host[i % nev];
+            xyz[3 * i] = node % n[0];
+            xyz[3 * i + 1] = node / n[0] % n[1];
+            xyz[3 * i + 2] = node / (n[0] * n[1]);
+        }
+    }
+    if (!hypo_all_in("mceik_mcmc_hypo_enable", xyz.data(), ne, nev, o->lo, o->hi)) return 1;
+    HypoDev &H = s->H;
+    if (!H.hyp) {                      // every array or none: a failed enable leaves the sampler as it was
+        HypoDev N;
+        memset(&N, 0, sizeof(N));
+        unsigned long long *cnt = nullptr;
+        if (dput(s, &N.hyp, xyz.data(), xyz.size()) || dalloc(s, &N.ev1, ne) || (nph > 1 && dalloc(s, &N.evall, ne * nph)) ||
+            dalloc(s, &N.ev2, 2 * ne * nph) || dalloc(s, &N.ttab2, 2 * ne * nph * D.nstat) || dalloc(s, &N.cand, 3 * ne) ||
+            dalloc(s, &N.acc, ne) || dalloc(s, &N.obj, 2 * ne) || dalloc(s, &N.logu, ne) || dalloc(s, &cnt, 2 * (size_t)nev) ||
+            dalloc(s, &N.mom, 9 * (size_t)nev))
+            return -1;
+        N.nx = n[0]; N.ny = n[1]; N.nz = n[2];
+        N.attempts = cnt;
+        N.accepts = cnt + nev;
+        HIPCHK(hypo_lists(D, N, s->stream));
+        HIPCHK(hipStreamSynchronize(s->stream));
+        H = N;
+        s->d_hcnt = cnt;
+        // from here on every chain has event lists of its own: a row per model of the batch
+        s->fb.ev_node = H.ev1;
+        s->fb.ev_stride = nev;
+        s->fb_all.ev_node = nph > 1 ? H.evall : H.ev1;
+        s->fb_all.ev_stride = nev;
+        // a hypocentre step: every current model at [current | candidate], tables of its own
+        s->fb_hyp = s->fb_all;
+        s->fb_hyp.slow = D.slow_cur;
+        s->fb_hyp.ev_node = H.ev2;
+        s->fb_hyp.nev = 2 * nev;
+        s->fb_hyp.ev_stride = 2 * nev;
+        s->fb_hyp.ttab = H.ttab2;
+        s->fb_hyp.solve_order = nullptr;
+        s->fb_hyp.solve_clock = nullptr;
+    }
+    HIPCHK(hipMemset(s->d_hcnt, 0, 2 * (size_t)nev * 8));
+    HIPCHK(hipMemset(H.mom, 0, 9 * (size_t)nev * 8));
+    s->hyp_n = 0;
+    H.dmx = o->dmax[0]; H.dmy = o->dmax[1]; H.dmz = o->dmax[2];
+    H.lox = o->lo[0]; H.loy = o->lo[1]; H.loz = o->lo[2];
+    H.hix = o->hi[0]; H.hiy = o->hi[1]; H.hiz = o->hi[2];
+    s->hypo_every = o->every;
+    s->hypo_on = true;
+    return pipes_refresh(s);
+}
+
+extern "C" int mceik_mcmc_hypo_disable(mceik_mcmc *s)
+{
+    if (!s) return 1;
+    s->hypo_on = false;                // host state only: queued steps keep the kernels they were queued with
+    return 0;
+}
+
+extern "C" int mceik_mcmc_hypo_get(mceik_mcmc *s, mceik_hypo_opts *o, int *xyz)
+{
+    if (!s || !s->H.hyp) return 1;
+    const HypoDev &H = s->H;
+    if (o) {
+        o->every = s->hypo_on ? s->hypo_every : 0;
+        o->dmax[0] = H.dmx; o->dmax[1] = H.dmy; o->dmax[2] = H.dmz;
+        o->lo[0] = H.lox; o->lo[1] = H.loy; o->lo[2] = H.loz;
+        o->hi[0] = H.hix; o->hi[1] = H.hiy; o->hi[2] = H.hiz;
+    }
+    if (xyz) {
+        DeviceScope dg(s->device);
+        HIPCHK(hipStreamSynchronize(s->stream));
+        HIPCHK(hipMemcpy(xyz, H.hyp, (size_t)s->D.nchains * s->D.nev * 3 * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+extern "C" int mceik_mcmc_hypo_set(mceik_mcmc *s, const int *xyz)
+{
+    if (!s || !s->H.hyp || !xyz) return 1;
+    const HypoDev &H = s->H;
+    const size_t ne = (size_t)s->D.nchains * s->D.nev;
+    const int glo[3] = {0, 0, 0}, ghi[3] = {H.nx - 1, H.ny - 1, H.nz - 1};
+    const int blo[3] = {H.lox, H.loy, H.loz}, bhi[3] = {H.hix, H.hiy, H.hiz};
+    if (!hypo_all_in("mceik_mcmc_hypo_set", xyz, ne, s->D.nev, s->hypo_on ? blo : glo, s->hypo_on ? bhi : ghi)) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    HIPCHK(hipMemcpy(H.hyp, xyz, ne * 3 * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hypo_lists(s->D, H, s->stream));
+    return forward_logl(s, "mceik_mcmc_hypo_set");
+}
+
+extern "C" int mceik_mcmc_hypo_stats(mceik_mcmc *s, long long *attempts, long long *accepts, int reset)
+{
+    if (!s || !s->H.hyp) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    const size_t n = (size_t)s->D.nev * 8;
+    if (attempts) HIPCHK(hipMemcpy(attempts, s->H.attempts, n, hipMemcpyDeviceToHost));
+    if (accepts) HIPCHK(hipMemcpy(accepts, s->H.accepts, n, hipMemcpyDeviceToHost));
+    if (reset) HIPCHK(hipMemset(s->d_hcnt, 0, 2 * n));
+    return 0;
+}
+
+extern "C" int mceik_mcmc_hypo_last(mceik_mcmc *s, int *cand, unsigned char *accept, double *obj)
+{
+    if (!s || !s->H.hyp) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    const size_t ne = (size_t)s->D.nchains * s->D.nev;
+    if (cand) HIPCHK(hipMemcpy(cand, s->H.cand, ne * 3 * sizeof(int), hipMemcpyDeviceToHost));
+    if (accept) HIPCHK(hipMemcpy(accept, s->H.acc, ne, hipMemcpyDeviceToHost));
+    if (obj) HIPCHK(hipMemcpy(obj, s->H.obj, ne * 2 * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int mceik_mcmc_hypo_moments_get(mceik_mcmc *s, long long *n, long long *sum, long long *sq)
+{
+    if (!s || !s->H.hyp) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    const int nev = s->D.nev;
+    std::vector<long long> m((size_t)nev * 9);
+    HIPCHK(hipMemcpy(m.data(), s->H.mom, m.size() * 8, hipMemcpyDeviceToHost));
+    if (n) *n = s->hyp_n;
+    for (int e = 0; e < nev; e++) {
+        for (int k = 0; k < 3 && sum; k++) sum[3 * e + k] = m[9 * (size_t)e + k];
+        for (int k = 0; k < 6 && sq; k++) sq[6 * e + k] = m[9 * (size_t)e + 3 + k];
+    }
+    return 0;
+}
+
+extern "C" int mceik_mcmc_hypo_moments_set(mceik_mcmc *s, long long n, const long long *sum, const long long *sq)
+{
+    if (!s || !s->H.hyp || n < 0 || !sum || !sq) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    const int nev = s->D.nev;
+    std::vector<long long> m((size_t)nev * 9);
+    for (int e = 0; e < nev; e++) {
+        for (int k = 0; k < 3; k++) m[9 * (size_t)e + k] = sum[3 * e + k];
+        for (int k = 0; k < 6; k++) m[9 * (size_t)e + 3 + k] = sq[6 * e + k];
+    }
+    HIPCHK(hipMemcpy(s->H.mom, m.data(), m.size() * 8, hipMemcpyHostToDevice));
+    s->hyp_n = n;
+    return 0;
+}
+
+extern "C" int mceik_hypo_draw(uint32_t seed, uint32_t gchain, uint64_t step, int e, const int dmax[3], int d[3],
+                               double *logu)
+{
+    if (e < 0 || !dmax || !d || dmax[0] < 0 || dmax[1] < 0 || dmax[2] < 0) return 1;
+    const uint32_t r3 = hypo_draw(seed, gchain, step, e, dmax[0], dmax[1], dmax[2], d);
+    if (logu) *logu = hypo_det_log_host(((double)r3 + 0.5) * (1.0 / 4294967296.0));
+    return 0;
+}
+
 int mcmc_post_ctx(mceik_mcmc *s, McmcPostCtx *out)
 {
     if (!s || !out) return 1;
@@ -377,6 +576,19 @@ extern "C" int mceik_mcmc_checkpoint(mceik_mcmc *s, int *v, double *logl, long l
     return 0;
 }
 
+// One forward of every model of every chain at the chains' positions, and
+// logL from it (not timed, not counted in the FSM stats).  Synchronises.
+static int forward_logl(mceik_mcmc *s, const char *who)
+{
+    unsigned long long keep[MCEIK_ITERS_N];
+    HIPCHK(hipMemcpy(keep, s->d_iters, sizeof(keep), hipMemcpyDeviceToHost));
+    if (mcmc_forward_all(s)) return -1;
+    HIPCHK(mcmc_init_loglik(s->D, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    HIPCHK(hipMemcpy(s->d_iters, keep, sizeof(keep), hipMemcpyHostToDevice));
+    return check_forward_ierr(s, who) ? 2 : 0;
+}
+
 extern "C" int mceik_mcmc_restore(mceik_mcmc *s, const int *v, const double *logl, const long long *naccept,
                                   long long step, int nkept)
 {
@@ -402,15 +614,8 @@ extern "C" int mceik_mcmc_restore(mceik_mcmc *s, const int *v, const double *log
     else HIPCHK(hipMemset(D.naccept, 0, (size_t)D.nchains * 8));
     if (logl) {
         HIPCHK(hipMemcpy(D.logl, logl, (size_t)D.nchains * 8, hipMemcpyHostToDevice));
-    } else {
-        // one forward of the restored models (not timed, not counted in the FSM stats)
-        unsigned long long keep[MCEIK_ITERS_N];
-        HIPCHK(hipMemcpy(keep, s->d_iters, sizeof(keep), hipMemcpyDeviceToHost));
-        if (mcmc_forward_all(s)) return -1;
-        HIPCHK(mcmc_init_loglik(D, s->stream));
-        HIPCHK(hipStreamSynchronize(s->stream));
-        HIPCHK(hipMemcpy(s->d_iters, keep, sizeof(keep), hipMemcpyHostToDevice));
-        if (check_forward_ierr(s, "mceik_mcmc_restore")) return 2;
+    } else if (int rc = forward_logl(s, "mceik_mcmc_restore")) {
+        return rc;
     }
     s->step = step;
     s->nkept = nkept;
@@ -497,7 +702,8 @@ extern "C" int mceik_mcmc_get_info(mceik_mcmc *s, mceik_mcmc_info *info)
     DeviceScope dg(s->device);
     memset(info, 0, sizeof(*info));
     info->npipe = s->npipe;
-    info->multi_step = s->persist && !s->block_on && !s->prior_on ? 1 : 0;   // block proposals and the prior step per launch
+    // block proposals, the prior and hypocentre moves step per launch
+    info->multi_step = s->persist && !s->block_on && !s->prior_on && !s->hypo_on ? 1 : 0;
     info->nphase = s->D.nphase;
     info->masked_s = s->masked_s;
     FsmLaunch L;

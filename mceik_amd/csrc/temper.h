@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "hypo.h"
 #include "mcmc_common.h"
 
 // One swap round of the whole sampler (D is the sampler's state, never a
@@ -12,6 +13,8 @@
 // chain p and upper chain p + G (rung p / G); pairs whose rung has the other
 // parity sit the round out.  gs is the Philox counter (the global step the
 // round belongs to).  flag: [(ntemps - 1) * G] ints of scratch; attempts,
-// accepts: [ntemps - 1] counters.  No host synchronisation.
+// accepts: [ntemps - 1] counters.  H (or null): the chains' hypocentres and
+// event lists, exchanged with the models.  No host synchronisation.
 hipError_t temper_swap_round(const McmcDev &D, int ntemps, int parity, uint64_t gs, int *flag,
-                             unsigned long long *attempts, unsigned long long *accepts, hipStream_t st);
+                             unsigned long long *attempts, unsigned long long *accepts, hipStream_t st,
+                             const HypoDev *H = nullptr);

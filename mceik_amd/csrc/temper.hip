@@ -124,7 +124,8 @@ __global__ __launch_bounds__(TEMPER_BLOCK) void temper_exchange_kernel(TemperRow
 }  // namespace
 
 hipError_t temper_swap_round(const McmcDev &D, int ntemps, int parity, uint64_t gs, int *flag,
-                             unsigned long long *attempts, unsigned long long *accepts, hipStream_t st)
+                             unsigned long long *attempts, unsigned long long *accepts, hipStream_t st,
+                             const HypoDev *H)
 {
     if (ntemps < 2 || !D.beta) return hipSuccess;
     const int G = D.nchains / ntemps, npairs = (ntemps - 1) * G;
@@ -143,6 +144,18 @@ hipError_t temper_swap_round(const McmcDev &D, int ntemps, int parity, uint64_t 
     for (int p0 = 0; p0 < npairs; p0 += TEMPER_MAX_GRID_Y) {
         const int np = npairs - p0 < TEMPER_MAX_GRID_Y ? npairs - p0 : TEMPER_MAX_GRID_Y;
         hipLaunchKernelGGL(temper_exchange_kernel, dim3(R.t4, np), dim3(TEMPER_BLOCK), 0, st, R, flag, p0, G);
+    }
+    if (H && H->hyp) {
+        // the positions and the event lists derived from them (hypo.h): rows of 3 nev, nev and nphase * nev ints
+        auto tiles = [](int len) { return (len + TEMPER_TILE - 1) / TEMPER_TILE; };
+        TemperRows Q;
+        Q.p0 = (unsigned *)H->hyp; Q.p1 = (unsigned *)H->ev1; Q.p2 = (unsigned *)H->evall; Q.p3 = nullptr;
+        Q.len0 = 3 * D.nev; Q.len1 = D.nev; Q.len2 = H->evall ? D.nphase * D.nev : 0; Q.len3 = 0;
+        Q.t1 = tiles(Q.len0); Q.t2 = Q.t1 + tiles(Q.len1); Q.t3 = Q.t2 + tiles(Q.len2); Q.t4 = Q.t3;
+        for (int p0 = 0; p0 < npairs; p0 += TEMPER_MAX_GRID_Y) {
+            const int np = npairs - p0 < TEMPER_MAX_GRID_Y ? npairs - p0 : TEMPER_MAX_GRID_Y;
+            hipLaunchKernelGGL(temper_exchange_kernel, dim3(Q.t4, np), dim3(TEMPER_BLOCK), 0, st, Q, flag, p0, G);
+        }
     }
     return hipGetLastError();
 }

@@ -224,6 +224,8 @@ class BatchSolver:
         (fp32): the node's value, or with ev_frac ([nev][3] float32 fractions,
         ev_node = the lowest corner of the event's cell; `cell_corners`) the
         trilinear interpolation in that cell (mceik_fsm_batch.ev_frac).
+        A 2-D ev_node [nmodel][nev] (ev_frac [nmodel][nev][3]) gives every model
+        of the batch a list of its own (mceik_fsm_batch.ev_stride = nev).
         solve_order: optional permutation of the nmodel*nstat solve ids (the
         order the work queues hand them out; results do not depend on it).
         solve_clock: also return out["clock"] [nsolve][2], the device realtime
@@ -245,7 +247,10 @@ class BatchSolver:
         if slow_mode == 1 and slow.dtype != torch.float32:
             raise TypeError("cell slowness must be float32")
         slow = slow.contiguous()
-        nev = 0 if ev_node is None else int(ev_node.numel())
+        per_model = ev_node is not None and ev_node.dim() == 2
+        if per_model and int(ev_node.shape[0]) != nmodel:
+            raise ValueError("a 2-D ev_node holds one row per model")
+        nev = 0 if ev_node is None else int(ev_node.shape[-1] if per_model else ev_node.numel())
         b = self.describe(nmodel, nstat, nsrc, slow_mode, nev, max_sweeps, max_waves, step_z)
         nsolve = nmodel * nstat
         niter = torch.zeros(nsolve, dtype=torch.int32, device=dev)
@@ -271,9 +276,10 @@ class BatchSolver:
             b.ev_node, b.ttab = ev_node.data_ptr(), ttab.data_ptr()
             out["ttab"] = ttab
             out["_ev"] = ev_node
+            b.ev_stride = nev if per_model else 0
             if ev_frac is not None:
                 ev_frac = torch.as_tensor(ev_frac, dtype=torch.float32).to(dev).contiguous()
-                if ev_frac.numel() != 3 * nev:
+                if ev_frac.numel() != 3 * ev_node.numel():
                     raise ValueError("ev_frac must hold 3 fractions per event")
                 b.ev_frac = ev_frac.data_ptr()
                 out["_evf"] = ev_frac

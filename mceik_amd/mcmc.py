@@ -399,6 +399,21 @@ def prior_delta(grid, v, cell, radius, amp, vref=None):
     return es.value, ed.value
 
 
+def hypo_draw(seed, gchain, step, e, dmax=(1, 1, 1)):
+    """The hypocentre draw of event `e` of global chain `gchain` at global step
+    `step` (mceik_hypo_draw; host only): (d int32 [3] in [-dmax, dmax] per axis,
+    log u)."""
+    dm = np.ascontiguousarray(dmax, dtype=np.int32).ravel()
+    if dm.size != 3:
+        raise ValueError("hypo_draw: dmax is one value per axis")
+    d, logu = np.zeros(3, np.int32), C.c_double(0.0)
+    rc = _lib.lib().mceik_hypo_draw(int(seed), int(gchain), int(step), int(e), dm.ctypes.data_as(C.c_void_p),
+                                    d.ctypes.data_as(C.c_void_p), C.byref(logu))
+    if rc != 0:
+        raise ValueError("hypo_draw: e >= 0 and every dmax >= 0")
+    return d, logu.value
+
+
 def prior_weight(sigma):
     """w = 1 / (2 sigma^2) per phase from a sigma in m/s: a scalar (both
     phases) or a (P, S) pair; None is weight 0."""
@@ -456,6 +471,8 @@ class Sampler:
         self._block = None              # (rmin, rmax) while block proposals are enabled
         self._block_base = None         # (attempts, accepts) of a restored checkpoint, as _temper_base
         self._prior = None              # (w_smooth, w_damp, vref digest) while the prior is enabled
+        self._hypo = None               # (every, dmax, lo, hi) while hypocentre moves are enabled
+        self._hypo_base = None          # (attempts, accepts) of a restored checkpoint, as _temper_base
 
     @property
     def model_shape(self):
@@ -554,6 +571,11 @@ class Sampler:
             ck["block"] = {"rmin": self._block[0], "rmax": self._block[1], "attempts": att, "accepts": acc}
         if self._prior is not None:      # the weights and the reference model decide what the chains sample
             ck["prior"] = {"w_smooth": self._prior[0], "w_damp": self._prior[1], "vref_sha256": self._prior[2]}
+        if self._hypo is not None:       # the positions are chain state; the options decide what is proposed
+            att, acc = self.hypo_stats()
+            n, sm, sq = self._hypo_moments()
+            ck["hypo"] = {"every": self._hypo[0], "dmax": self._hypo[1], "lo": self._hypo[2], "hi": self._hypo[3],
+                          "xyz": self.hypo_positions(), "attempts": att, "accepts": acc, "n": n, "sum": sm, "sq": sq}
         return ck
 
     def restore(self, ck, recompute_logl=False):
@@ -573,6 +595,11 @@ class Sampler:
         if pk is not None and (self._prior is None or
                                (tuple(pk["w_smooth"]), tuple(pk["w_damp"]), pk["vref_sha256"]) != self._prior):
             raise ValueError("the checkpoint was taken with other prior weights or another reference model")
+        hk = ck.get("hypo")              # likewise
+        if hk is not None:
+            if self._hypo is None or (int(hk["every"]), tuple(hk["dmax"]), tuple(hk["lo"]), tuple(hk["hi"])) != self._hypo:
+                raise ValueError("the checkpoint was taken with other hypocentre-move options")
+            self.hypo_set(hk["xyz"])     # (its forward is at the old models: the restore below sets logL)
         v = np.ascontiguousarray(ck["v"], dtype=np.int32)
         assert v.shape == self.model_shape
         logl = None if recompute_logl else np.ascontiguousarray(ck["logl"], dtype=np.float64)
@@ -592,6 +619,16 @@ class Sampler:
         if bk is not None:
             self.block_stats(reset=True)
             self._block_base = (np.asarray(bk["attempts"], np.int64).copy(), np.asarray(bk["accepts"], np.int64).copy())
+        if hk is not None:
+            self.hypo_stats(reset=True)
+            self._hypo_base = (np.asarray(hk["attempts"], np.int64).copy(), np.asarray(hk["accepts"], np.int64).copy())
+            sm = np.ascontiguousarray(hk["sum"], dtype=np.int64)
+            sq = np.ascontiguousarray(hk["sq"], dtype=np.int64)
+            assert sm.shape == (self.p.nevents, 3) and sq.shape == (self.p.nevents, 6)
+            rc = self._L.mceik_mcmc_hypo_moments_set(self._h, int(hk["n"]), sm.ctypes.data_as(C.c_void_p),
+                                                     sq.ctypes.data_as(C.c_void_p))
+            if rc != 0:
+                raise RuntimeError(f"mceik_mcmc_hypo_moments_set failed ({rc})")
 
     # --- streaming posterior (include/mceik.h mceik_mcmc_posterior_*) ---
     def posterior_enable(self, per_chain=True, nbins=64):
@@ -823,6 +860,122 @@ class Sampler:
         if rc != 0:
             raise RuntimeError(f"mceik_mcmc_prior_last failed ({rc})")
         return de
+
+    # --- hypocentre moves (include/mceik.h mceik_mcmc_hypo_*) ---
+    def hypo_enable(self, every, dmax=(1, 1, 1), box=None):
+        """Sample the event hypocentres with the velocity models: every chain
+        carries a node (ix, iy, iz) per event, which starts at the catalogue's
+        snapped node at the first enable.  With every = K > 0 global step gs is
+        a hypocentre step iff gs % K == K - 1: instead of a velocity proposal
+        every event of every chain draws a move of up to `dmax` nodes per axis
+        and accepts or rejects it on its own (one forward of the chain's
+        current models serves them all).  `box` = (lo, hi), two node triples
+        (inclusive), bounds the positions; None is the whole grid.  Every step
+        is then one launch (`info()["multi_step"]` is False until
+        `hypo_disable`).  Resets the counters and the moments."""
+        p = self.p
+        lo, hi = ((0, 0, 0), (p.nx - 1, p.ny - 1, p.nz - 1)) if box is None else box
+        dm, lo, hi = (tuple(int(x) for x in np.ravel(a)) for a in (dmax, lo, hi))
+        if not (len(dm) == len(lo) == len(hi) == 3):
+            raise ValueError("hypo_enable: dmax and the box corners are one value per axis")
+        o = _lib.HypoOpts()
+        o.every = int(every)
+        for a in range(3):
+            o.dmax[a], o.lo[a], o.hi[a] = dm[a], lo[a], hi[a]
+        rc = self._L.mceik_mcmc_hypo_enable(self._h, C.byref(o))
+        if rc != 0:
+            raise (ValueError if rc == 1 else RuntimeError)(
+                f"mceik_mcmc_hypo_enable failed ({rc}): every >= 0, dmax >= 0, a box lo <= hi inside the grid that holds "
+                "every chain's positions, tt_interp = 0, and no states in an enabled posterior")
+        self._hypo = (int(every), dm, lo, hi)
+        self._hypo_base = None
+
+    def hypo_disable(self):
+        """Later steps are velocity steps again; the positions stay where they are, per chain."""
+        if self._L.mceik_mcmc_hypo_disable(self._h) != 0:
+            raise RuntimeError("mceik_mcmc_hypo_disable failed")
+        self._hypo = None
+        self._hypo_base = None
+
+    def hypo_positions(self):
+        """int32 [nchains, nev, 3]: every chain's node (ix, iy, iz) per event (after a first `hypo_enable`)."""
+        xyz = np.empty((self.nchains, self.p.nevents, 3), np.int32)
+        rc = self._L.mceik_mcmc_hypo_get(self._h, None, xyz.ctypes.data_as(C.c_void_p))
+        if rc != 0:
+            raise RuntimeError(f"mceik_mcmc_hypo_get failed ({rc}): hypocentre moves were never enabled")
+        return xyz
+
+    def hypo_set(self, xyz):
+        """Replace the positions (int [nchains, nev, 3], inside the grid, inside
+        the box while enabled); one full forward recomputes logL."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.int32)
+        if xyz.shape != (self.nchains, self.p.nevents, 3):
+            raise ValueError(f"hypo_set: positions shaped {(self.nchains, self.p.nevents, 3)}, not {xyz.shape}")
+        rc = self._L.mceik_mcmc_hypo_set(self._h, xyz.ctypes.data_as(C.c_void_p))
+        if rc != 0:
+            raise (ValueError if rc == 1 else RuntimeError)(
+                f"mceik_mcmc_hypo_set failed ({rc}): after a first hypo_enable, positions inside the grid / the box")
+        self._last_full = True
+
+    def hypo_stats(self, reset=False):
+        """(attempts, accepts) int64 [nev]: moves tried and accepted per event, over the chains."""
+        n = self.p.nevents
+        att, acc = np.zeros(n, np.int64), np.zeros(n, np.int64)
+        rc = self._L.mceik_mcmc_hypo_stats(self._h, att.ctypes.data_as(C.c_void_p), acc.ctypes.data_as(C.c_void_p),
+                                           int(reset))
+        if rc != 0:
+            raise RuntimeError(f"mceik_mcmc_hypo_stats failed ({rc})")
+        if self._hypo_base is not None:
+            att, acc = att + self._hypo_base[0], acc + self._hypo_base[1]
+        if reset:
+            self._hypo_base = None
+        return att, acc
+
+    def hypo_last(self):
+        """The last hypocentre step: (cand int32 [nchains, nev, 3] = current + d,
+        accept uint8 [nchains, nev], obj float64 [nchains, nev, 2] = objfn at the
+        current and at the candidate node)."""
+        nch, nev = self.nchains, self.p.nevents
+        cand, acc, obj = np.zeros((nch, nev, 3), np.int32), np.zeros((nch, nev), np.uint8), np.zeros((nch, nev, 2))
+        rc = self._L.mceik_mcmc_hypo_last(self._h, cand.ctypes.data_as(C.c_void_p), acc.ctypes.data_as(C.c_void_p),
+                                          obj.ctypes.data_as(C.c_void_p))
+        if rc != 0:
+            raise RuntimeError(f"mceik_mcmc_hypo_last failed ({rc})")
+        return cand, acc, obj
+
+    def _hypo_moments(self):
+        """(n, sum int64 [nev, 3], sq int64 [nev, 6]): the exact moments of the cold chains' kept positions."""
+        nev = self.p.nevents
+        n, sm, sq = C.c_longlong(0), np.zeros((nev, 3), np.int64), np.zeros((nev, 6), np.int64)
+        rc = self._L.mceik_mcmc_hypo_moments_get(self._h, C.byref(n), sm.ctypes.data_as(C.c_void_p),
+                                                 sq.ctypes.data_as(C.c_void_p))
+        if rc != 0:
+            raise RuntimeError(f"mceik_mcmc_hypo_moments_get failed ({rc})")
+        return n.value, sm, sq
+
+    def hypo_moments(self):
+        """{"n", "sum" [nev, 3], "sq" [nev, 6] = (xx, yy, zz, xy, xz, yz)}: exact
+        int64 sums of the cold chains' positions (nodes) over the kept steps
+        since `hypo_enable`; ranks merge them by addition."""
+        n, sm, sq = self._hypo_moments()
+        return {"n": n, "sum": sm, "sq": sq}
+
+    def hypo_summary(self, moments=None):
+        """(mean [nev, 3] in metres = origin + h * mean node, cov [nev, 3, 3] in
+        m^2) of every event's location over the cold chains' kept states, from
+        the moments (this sampler's, or merged ones); NaN without states."""
+        m = self.hypo_moments() if moments is None else moments
+        n = int(m["n"])
+        p = self.p
+        sm, sq = np.asarray(m["sum"], np.float64), np.asarray(m["sq"], np.float64)
+        if n <= 0:
+            return np.full((p.nevents, 3), np.nan), np.full((p.nevents, 3, 3), np.nan)
+        mu = sm / n
+        second = np.empty((p.nevents, 3, 3))
+        for k, (a, b) in enumerate(((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2))):
+            second[:, a, b] = second[:, b, a] = sq[:, k] / n
+        cov = (second - mu[:, :, None] * mu[:, None, :]) * (p.h * p.h)
+        return np.array([p.x0, p.y0, p.z0]) + p.h * mu, cov
 
     def fsm_stats(self, reset=False):
         """(FSM kernel ms from hipEvents, launches, executed iterations summed over
