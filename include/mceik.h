@@ -461,6 +461,122 @@ int mceik_mcmc_hypo_moments_set(mceik_mcmc *s, long long n, const long long *sum
  * global step `step`: d[3] and log u (may be NULL). */
 int mceik_hypo_draw(uint32_t seed, uint32_t gchain, uint64_t step, int e, const int dmax[3], int d[3], double *logu);
 
+/* ---- noise scale and station statics (csrc/nuis.hip) -----
+ * Off by default; with it off nothing changes: every chain takes the pick
+ * uncertainty var[j] and the station corrections tcorr[j] from the catalogue.
+ * Enabled, every chain carries integer state of its own:
+ *   kn[nchains][nphase]         index into a noise ladder lam[nk], lnlam[nk]
+ *                               (fp64 tables the caller passes; nk odd, the
+ *                               middle entry exactly lam = 1, lnlam = 0: the
+ *                               start value), uniform prior on the index;
+ *   kc[nchains][nphase][nstat]  station static in units of dt seconds, uniform
+ *                               prior on |kc| <= kcmax, start value 0.
+ * The effective observations of chain c take one fp64 operation each,
+ *   var_eff[j]   = var[j] * lam[kn[c][ph(j)]]
+ *   tcorr_eff[j] = tcorr[j] + (double)kc[c][ph(j)][stat(j)] * dt
+ *   logL[c]      = (((0 - obj_0) - obj_1) ... - obj_{nev-1}) - norm[0] * lnlam[kn[c][0]]
+ *                                                  (two models: - norm[1] * lnlam[kn[c][1]])
+ * with obj_e the sampler's objfn of event e on the effective arrays (the same
+ * operations in the same order) and norm[ph] an option (NULL: the number of
+ * used, unmasked picks of phase ph).  var enters objfn as 1 / var on the
+ * residual, so lam scales sigma and the term is the Gaussian normalisation
+ * with the origin time at its plug-in value (the profile form; a caller may
+ * pass norm[ph] reduced by the events' degrees of freedom).  At the start
+ * values every logL is today's bit for bit.  While a sampler holds this state
+ * every logL it evaluates honours it -- velocity accepts (single cell, block),
+ * hypocentre moves, restore with logl NULL -- every step is one launch of each
+ * kernel (mceik_mcmc_info.multi_step reports 0), and a one-model sampler keeps
+ * the tables of its current model, as a two-model sampler always does.
+ *
+ * Global step gs is a nuisance step iff gs % every == offset (a step that is
+ * also a hypocentre step is a hypocentre step).  It replaces that step's
+ * velocity proposal and runs no eikonal solve: v and naccept do not change,
+ * mceik_mcmc_last's accept flags are 0, the kept-state and posterior rules
+ * apply with the new logL, a swap round of gs runs first.  A chain (global id
+ * g) runs nsub sub-moves in sequence, sub-move `sub` drawing
+ *   r = Philox4x32-10(counter {(uint32)gs, (uint32)(gs >> 32), 3, sub}, key {g, seed})
+ *   M = (noise: nphase) + (statics: nact[0] + nact[1]),  q = (r0 * M) >> 32
+ * where nact[ph] counts the stations with a used pick of phase ph (a phase
+ * with fewer than two counts 0: it has no statics moves).
+ *   q < nphase (noise on): a noise move of phase q, k' = k +- d,
+ *     d = 1 + ((r1 * dk) >> 32), minus iff r2 & 1; k' outside [0, nk) is rejected.
+ *   otherwise a statics move of a zero-sum pair of one phase: a = the q-th of
+ *     the remaining range over the phases' active stations (station order),
+ *     partner b = (r1 * (nact - 1)) >> 32, b += (b >= a),
+ *     mag = 1 + (((r2 >> 1) * dc) >> 31), minus iff r2 & 1;
+ *     kc[a] += s mag, kc[b] -= s mag, rejected if either leaves the box.  The
+ *     pair keeps the phase's sum of statics at its start value exactly: the
+ *     direction the analytic origin time absorbs is never moved along.
+ *   log u = det_log((r3 + 0.5) / 2^32); accept iff log u < logL' - logL
+ *     (tempering: log u < beta * (logL' - logL); the boxes are not tempered).
+ * Both draws are symmetric: no Hastings term.  A tempering swap exchanges the
+ * two chains' kn, kc, effective observations and current tables with their
+ * models; its rule does not change.
+ *
+ * After every kept step (nburnIn / keepK) while enabled the cold chains add
+ * to exact integer moments: n states, per phase the sums of k and k^2 and a
+ * histogram over the ladder, per (phase, station) the sums of kc and kc^2;
+ * pipes and ranks merge them by addition.
+ *
+ * enable refuses (1): NULL options, both parts off, every <= 0, offset
+ * outside [0, every), nsub <= 0, nk even or a ladder whose middle entry is not
+ * exactly (1, 0) (lam and lnlam may both be NULL with noise off), dk, dc or
+ * kcmax negative, dt <= 0 with statics on, nothing to move, held state that
+ * does not fit the new ladder length or box, 8 nev + 4 nphase nstat above
+ * 64 KiB, and an enabled posterior that holds states.  tt_interp = 1 is
+ * allowed.  enable runs one full forward (not counted in the FSM statistics).
+ * disable stops the nuisance steps and keeps the values; clear returns every
+ * chain to the start values, recomputes logL and gives multi-step launches
+ * back.  The other functions return 1 while no state is held.  A checkpoint
+ * is mceik_mcmc_checkpoint plus nuis_get and nuis_moments_get; a resume is
+ * nuis_set, then mceik_mcmc_restore with logl NULL (its forward makes the
+ * current tables; it gives the saved logl), then nuis_moments_set.  The values
+ * are not part of the kept ring nor of mceik_mcmc_gather.
+ *
+ * Every function returns 0, 1 on invalid arguments or -1 on a device failure. */
+typedef struct mceik_nuis_opts {
+    int every, offset, nsub;
+    int noise, statics;            /* which parts move (either or both) */
+    int nk, dk;                    /* ladder entries; a noise move is +-[1, max(dk, 1)] entries */
+    int dc, kcmax;                 /* a statics move is +-[1, max(dc, 1)] units; the box */
+    double dt;                     /* seconds per unit of kc */
+    const double *lam, *lnlam;     /* [nk] */
+    const double *norm;            /* [nphase] or NULL */
+} mceik_nuis_opts;
+/* Turns the moves on (or replaces the options; held values stay).  Synchronises;
+ * resets the counters and the moments. */
+int mceik_mcmc_nuis_enable(mceik_mcmc *s, const mceik_nuis_opts *o);
+int mceik_mcmc_nuis_disable(mceik_mcmc *s);
+int mceik_mcmc_nuis_clear(mceik_mcmc *s);
+/* The options in force (every = 0 after disable; the pointers of o are NULL),
+ * the ladder [nk], norm [nphase], kn [nchains][nphase] and kc
+ * [nchains][nphase][nstat].  Any may be NULL.  Synchronises. */
+int mceik_mcmc_nuis_get(mceik_mcmc *s, mceik_nuis_opts *o, double *lam, double *lnlam, double *norm, int *kn, int *kc);
+/* Replaces the values (inside the ladder and the box) and recomputes logL
+ * from the current tables the sampler holds: no eikonal solve.  Synchronises. */
+int mceik_mcmc_nuis_set(mceik_mcmc *s, const int *kn, const int *kc);
+/* attempts, accepts [nphase + nphase * nstat] over the chains: entry ph is the
+ * noise index of phase ph, entry nphase + ph * nstat + k the static of station
+ * k (a pair counts on both its stations).  Either may be NULL.  Synchronises. */
+int mceik_mcmc_nuis_stats(mceik_mcmc *s, long long *attempts, long long *accepts, int reset);
+/* The last nuisance step: rec [nchains][nsub][4] = parameter (numbered as in
+ * nuis_stats), partner parameter (-1: a noise move), candidate value of the
+ * parameter, accepted; logl [nchains][nsub][2] = logL before the sub-move and
+ * logL' of the candidate (a candidate outside its box: logL).  Synchronises. */
+int mceik_mcmc_nuis_last(mceik_mcmc *s, int *rec, double *logl);
+/* The moments: n, ksum [nphase][2] = sums of k, k^2, hist [nphase][nk], csum
+ * [nphase][nstat][2] = sums of kc, kc^2 (get: any may be NULL). */
+int mceik_mcmc_nuis_moments_get(mceik_mcmc *s, long long *n, long long *ksum, long long *hist, long long *csum);
+int mceik_mcmc_nuis_moments_set(mceik_mcmc *s, long long n, const long long *ksum, const long long *hist,
+                                const long long *csum);
+/* Host only (no GPU call): sub-move `sub` of global chain gchain at global
+ * step `step` with nnoise = (noise: nphase, else 0) and nact0 / nact1 active
+ * stations per phase (0 or >= 2): m = {kind (0 noise, 1 statics), phase, a, b
+ * (indices into the phase's active stations; 0 for a noise move), signed
+ * step} and log u (may be NULL). */
+int mceik_nuis_draw(uint32_t seed, uint32_t gchain, uint64_t step, int sub, int nnoise, int nact0, int nact1, int dk,
+                    int dc, int m[5], double *logu);
+
 /* ---- multi-rank runs (one process per GPU; csrc/comm.hip) ---------------
  * The sampler's only collective is the checkpoint gather (SURVEY s.8e) over
  * RCCL (xGMI on one node).  Bootstrap as RCCL's: rank 0 calls

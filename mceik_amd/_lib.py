@@ -119,6 +119,13 @@ class HypoOpts(C.Structure):
     _fields_ = [("every", C.c_int), ("dmax", C.c_int * 3), ("lo", C.c_int * 3), ("hi", C.c_int * 3)]
 
 
+class NuisOpts(C.Structure):
+    """mceik_nuis_opts (include/mceik.h)."""
+    _fields_ = [("every", C.c_int), ("offset", C.c_int), ("nsub", C.c_int), ("noise", C.c_int), ("statics", C.c_int),
+                ("nk", C.c_int), ("dk", C.c_int), ("dc", C.c_int), ("kcmax", C.c_int), ("dt", C.c_double),
+                ("lam", C.c_void_p), ("lnlam", C.c_void_p), ("norm", C.c_void_p)]
+
+
 # every extern "C" symbol include/*.h declares
 EXPORTS = ("eikonal3d_serial_driver", "eikonal3d_serial_driver_sp", "eikonal3d_batch_solve", "eikonal3d_initialize", "eikonal3d_solve",
            "eikonal3d_finalize", "locate3d_gridsearch__double64", "locate3d_gridsearch__float64",
@@ -144,6 +151,9 @@ EXPORTS = ("eikonal3d_serial_driver", "eikonal3d_serial_driver_sp", "eikonal3d_b
            "mceik_mcmc_hypo_enable", "mceik_mcmc_hypo_disable", "mceik_mcmc_hypo_get", "mceik_mcmc_hypo_set",
            "mceik_mcmc_hypo_stats", "mceik_mcmc_hypo_last", "mceik_mcmc_hypo_moments_get",
            "mceik_mcmc_hypo_moments_set", "mceik_hypo_draw",
+           "mceik_mcmc_nuis_enable", "mceik_mcmc_nuis_disable", "mceik_mcmc_nuis_clear", "mceik_mcmc_nuis_get",
+           "mceik_mcmc_nuis_set", "mceik_mcmc_nuis_stats", "mceik_mcmc_nuis_last", "mceik_mcmc_nuis_moments_get",
+           "mceik_mcmc_nuis_moments_set", "mceik_nuis_draw",
            "mceik_parms_defaults", "mceik_parms_set", "mceik_parms_read", "mceik_parms_args", "mceik_parms_write",
            "mceik_comm_available", "mceik_comm_unique_id", "mceik_comm_init", "mceik_comm_finalize", "mceik_mcmc_gather",
            "os_path_exists", "os_path_isdir", "os_path_isfile", "os_makedirs", "os_mkdir")
@@ -308,5 +318,24 @@ def lib():
     L.mceik_hypo_draw.restype = C.c_int
     L.mceik_hypo_draw.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p,
                                   C.POINTER(C.c_double)]
+    L.mceik_mcmc_nuis_enable.restype = C.c_int
+    L.mceik_mcmc_nuis_enable.argtypes = [C.c_void_p, C.POINTER(NuisOpts)]
+    for name in ("mceik_mcmc_nuis_disable", "mceik_mcmc_nuis_clear"):
+        getattr(L, name).restype = C.c_int
+        getattr(L, name).argtypes = [C.c_void_p]
+    L.mceik_mcmc_nuis_get.restype = C.c_int
+    L.mceik_mcmc_nuis_get.argtypes = [C.c_void_p, C.POINTER(NuisOpts)] + [C.c_void_p] * 5
+    L.mceik_mcmc_nuis_set.restype = C.c_int
+    L.mceik_mcmc_nuis_set.argtypes = [C.c_void_p] * 3
+    L.mceik_mcmc_nuis_stats.restype = C.c_int
+    L.mceik_mcmc_nuis_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.mceik_mcmc_nuis_last.restype = C.c_int
+    L.mceik_mcmc_nuis_last.argtypes = [C.c_void_p] * 3
+    L.mceik_mcmc_nuis_moments_get.restype = C.c_int
+    L.mceik_mcmc_nuis_moments_get.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)] + [C.c_void_p] * 3
+    L.mceik_mcmc_nuis_moments_set.restype = C.c_int
+    L.mceik_mcmc_nuis_moments_set.argtypes = [C.c_void_p, C.c_longlong] + [C.c_void_p] * 3
+    L.mceik_nuis_draw.restype = C.c_int
+    L.mceik_nuis_draw.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64] + [C.c_int] * 6 + [C.c_void_p, C.POINTER(C.c_double)]
     _lib = L
     return L

@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include "mcmc_common.h"
+#include "nuis.h"
 
 #define MCEIK_BLOCK_RMAX 8          // largest radius (inversion cells): 17^3 candidates
 
@@ -54,4 +55,4 @@ __host__ __device__ inline int block_dv(int ncx, int ncy, int ncz, int cx, int c
 hipError_t block_propose(const McmcDev &D, const BlockDev &B, uint64_t step, hipStream_t st);
 // Metropolis accept/reject of the pending block proposals and, with keep_slot
 // >= 0, the kept-state copy (as mcmc_accept).
-hipError_t block_accept(const McmcDev &D, const BlockDev &B, int keep_slot, hipStream_t st);
+hipError_t block_accept(const McmcDev &D, const BlockDev &B, const NuisDev &N, int keep_slot, hipStream_t st);

@@ -14,6 +14,7 @@
 #include "mcmc_common.h"
 #include "mcmc_device.h"
 #include "mcmc_host.h"
+#include "nuis.h"
 
 #define BLOCK_THREADS 256
 #define BLOCK_CHAINS (BLOCK_THREADS / 64)
@@ -72,7 +73,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void block_propose_kernel(McmcDev D,
 // accept_kernel's decision for chain (wave) c, every lane alike; lane 0 writes
 // the chain's scalars, the wave commits (v, slow_cur) or reverts (slow_prop)
 // the footprint and, with two models, copies the accepted phase's tables.
-__global__ __launch_bounds__(BLOCK_THREADS) void block_accept_kernel(McmcDev D, BlockDev B, int keep_slot)
+__global__ __launch_bounds__(BLOCK_THREADS) void block_accept_kernel(McmcDev D, BlockDev B, NuisDev N, int keep_slot)
 {
     const int c = blockIdx.x * BLOCK_CHAINS + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (c >= D.nchains) return;
@@ -82,7 +83,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void block_accept_kernel(McmcDev D, 
     int acc = 0;
     double ln = 0.0;
     if (inp) {
-        ln = mcmcd::chain_loglik(D, c, ph);
+        ln = nuis_logl(D, N, c, mcmcd::chain_loglik(nuis_chain(D, N, c), c, ph));
         const double d = ln - lold;
         acc = D.beta ? D.prop_logu[c] < D.beta[c] * d : D.prop_logu[c] < d;
         const int cc = cell - ph * D.ncell;
@@ -101,7 +102,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void block_accept_kernel(McmcDev D, 
                 D.slow_prop[row + t] = D.slow_cur[row + t];
             }
         }
-        if (acc && D.nphase > 1) mcmcd::chain_copy_tables(D, c, ph, lane, 64);
+        if (acc && D.ttab_cur) mcmcd::chain_copy_tables(D, c, ph, lane, 64);
     }
     if (lane == 0) {
         if (acc) {
@@ -124,10 +125,10 @@ hipError_t block_propose(const McmcDev &D, const BlockDev &B, uint64_t step, hip
     return hipGetLastError();
 }
 
-hipError_t block_accept(const McmcDev &D, const BlockDev &B, int keep_slot, hipStream_t st)
+hipError_t block_accept(const McmcDev &D, const BlockDev &B, const NuisDev &N, int keep_slot, hipStream_t st)
 {
     hipLaunchKernelGGL(block_accept_kernel, dim3((D.nchains + BLOCK_CHAINS - 1) / BLOCK_CHAINS), dim3(BLOCK_THREADS),
-                       0, st, D, B, keep_slot);
+                       0, st, D, B, N, keep_slot);
     if (keep_slot >= 0) return mcmc_keep(D, keep_slot, st);
     return hipGetLastError();
 }

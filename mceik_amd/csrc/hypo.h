@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "mcmc_common.h"
+#include "nuis.h"
 
 // Per-chain arrays are views (sampler.hip dev_view): a pipe's HypoDev points
 // at its chains' rows.  The counters and moments are the sampler's.
@@ -58,7 +59,7 @@ double hypo_det_log_host(double x);
 // candidate] lists before the forward ...
 hipError_t hypo_propose(const McmcDev &D, const HypoDev &H, uint64_t gs, hipStream_t st);
 // ... and, after it, the per-event accepts, then the chains' logL (and kept logL / state: keep_slot >= 0).
-hipError_t hypo_accept(const McmcDev &D, const HypoDev &H, int keep_slot, hipStream_t st);
+hipError_t hypo_accept(const McmcDev &D, const HypoDev &H, const NuisDev &N, int keep_slot, hipStream_t st);
 // Adds the first ncold chains' positions of H to the moments.
 hipError_t hypo_moments(const McmcDev &D, const HypoDev &H, int ncold, hipStream_t st);
 // ev1 (and evall) from hyp, every chain of D / H.

@@ -16,6 +16,7 @@
 #include "mcmc_common.h"
 #include "mcmc_device.h"
 #include "mcmc_host.h"
+#include "nuis.h"
 
 namespace {
 
@@ -84,12 +85,13 @@ __device__ __forceinline__ double hypo_event_obj(const McmcDev &D, const HypoDev
 // multiply; the uniform box is not tempered).  An accepted event's position,
 // list entries and (nphase 2) current-table columns move here; events touch
 // disjoint entries.
-__global__ __launch_bounds__(64) void hypo_accept_kernel(McmcDev D, HypoDev H)
+__global__ __launch_bounds__(64) void hypo_accept_kernel(McmcDev D, HypoDev H, NuisDev N)
 {
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= D.nchains * D.nev) return;
     const int c = i / D.nev, e = i - c * D.nev;
-    const double oc = hypo_event_obj(D, H, c, e, e), od = hypo_event_obj(D, H, c, e, D.nev + e);
+    const McmcDev E = nuis_chain(D, N, c);      // the chain's effective observations (nuisance state)
+    const double oc = hypo_event_obj(E, H, c, e, e), od = hypo_event_obj(E, H, c, e, D.nev + e);
     const int cx = H.cand[3 * i], cy = H.cand[3 * i + 1], cz = H.cand[3 * i + 2];
     const double dl = oc - od;
     int a = 0;
@@ -116,7 +118,7 @@ __global__ __launch_bounds__(64) void hypo_accept_kernel(McmcDev D, HypoDev H)
 // The chain's logL from the accepted sides, events in order: bitwise what a
 // full forward at the chain's models and new positions gives.  The step
 // proposed no velocity: its accept flag is 0.
-__global__ __launch_bounds__(64) void hypo_logl_kernel(McmcDev D, HypoDev H, int keep_slot)
+__global__ __launch_bounds__(64) void hypo_logl_kernel(McmcDev D, HypoDev H, NuisDev N, int keep_slot)
 {
     const int c = blockIdx.x * 64 + threadIdx.x;
     if (c >= D.nchains) return;
@@ -125,6 +127,7 @@ __global__ __launch_bounds__(64) void hypo_logl_kernel(McmcDev D, HypoDev H, int
         const size_t i = (size_t)c * D.nev + e;
         logl = logl - H.obj[2 * i + (H.acc[i] ? 1 : 0)];
     }
+    logl = nuis_logl(D, N, c, logl);
     D.logl[c] = logl;
     D.accept[c] = 0;
     if (keep_slot >= 0) D.keep_logl[(size_t)keep_slot * D.keep_stride + c] = logl;
@@ -188,11 +191,11 @@ hipError_t hypo_propose(const McmcDev &D, const HypoDev &H, uint64_t gs, hipStre
     return hipGetLastError();
 }
 
-hipError_t hypo_accept(const McmcDev &D, const HypoDev &H, int keep_slot, hipStream_t st)
+hipError_t hypo_accept(const McmcDev &D, const HypoDev &H, const NuisDev &N, int keep_slot, hipStream_t st)
 {
     const int n = D.nchains * D.nev;
-    hipLaunchKernelGGL(hypo_accept_kernel, dim3((n + 63) / 64), dim3(64), 0, st, D, H);
-    hipLaunchKernelGGL(hypo_logl_kernel, dim3((D.nchains + 63) / 64), dim3(64), 0, st, D, H, keep_slot);
+    hipLaunchKernelGGL(hypo_accept_kernel, dim3((n + 63) / 64), dim3(64), 0, st, D, H, N);
+    hipLaunchKernelGGL(hypo_logl_kernel, dim3((D.nchains + 63) / 64), dim3(64), 0, st, D, H, N, keep_slot);
     if (keep_slot >= 0) return mcmc_keep(D, keep_slot, st);
     return hipGetLastError();
 }

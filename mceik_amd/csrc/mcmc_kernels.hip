@@ -10,6 +10,7 @@
 #include "mcmc_common.h"
 #include "mcmc_device.h"
 #include "mcmc_host.h"
+#include "nuis.h"
 
 namespace {
 
@@ -22,22 +23,25 @@ __global__ void propose_kernel(McmcDev D, uint64_t step)
     mcmcd::chain_propose(D, c, step);
 }
 
-__global__ void init_loglik_kernel(McmcDev D)
+// (the current tables where the sampler keeps them: two models, or nuisance
+// state; the chain's effective observations and noise term with the latter)
+__global__ void init_loglik_kernel(McmcDev D, NuisDev N)
 {
     int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= D.nchains) return;
-    D.logl[c] = mcmcd::chain_loglik(D, c, D.nphase > 1 ? -1 : 0);
+    D.logl[c] = nuis_logl(D, N, c, mcmcd::chain_loglik(nuis_chain(D, N, c), c, D.ttab_cur ? -1 : 0));
 }
 
-// Metropolis accept/reject (mcmc_device.h chain_accept); with two models an
-// accepted proposal's tables become its phase's current tables.
-__global__ void accept_kernel(McmcDev D, int keep_slot)
+// Metropolis accept/reject (mcmc_device.h chain_accept); where the sampler
+// keeps current tables (two models, or nuisance state) an accepted proposal's
+// tables become its phase's current tables.
+__global__ void accept_kernel(McmcDev D, NuisDev N, int keep_slot)
 {
     int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= D.nchains) return;
     const int inp = D.prop_inprior[c], ph = D.prop_phase[c];
-    const double ln = inp ? mcmcd::chain_loglik(D, c, ph) : 0.0;
-    if (mcmcd::chain_accept(D, c, ln, keep_slot) && D.nphase > 1) mcmcd::chain_copy_tables(D, c, ph, 0, 1);
+    const double ln = inp ? nuis_logl(D, N, c, mcmcd::chain_loglik(nuis_chain(D, N, c), c, ph)) : 0.0;
+    if (mcmcd::chain_accept(D, c, ln, keep_slot) && D.ttab_cur) mcmcd::chain_copy_tables(D, c, ph, 0, 1);
 }
 
 // Kept state copy: [slot][chain][nphase][ncell] int (after accept_kernel).
@@ -314,15 +318,15 @@ hipError_t mcmc_propose(const McmcDev &D, uint64_t step, hipStream_t st)
     return hipGetLastError();
 }
 
-hipError_t mcmc_init_loglik(const McmcDev &D, hipStream_t st)
+hipError_t mcmc_init_loglik(const McmcDev &D, const NuisDev &N, hipStream_t st)
 {
-    hipLaunchKernelGGL(init_loglik_kernel, dim3((D.nchains + 63) / 64), dim3(64), 0, st, D);
+    hipLaunchKernelGGL(init_loglik_kernel, dim3((D.nchains + 63) / 64), dim3(64), 0, st, D, N);
     return hipGetLastError();
 }
 
-hipError_t mcmc_accept(const McmcDev &D, int keep_slot, hipStream_t st)
+hipError_t mcmc_accept(const McmcDev &D, const NuisDev &N, int keep_slot, hipStream_t st)
 {
-    hipLaunchKernelGGL(accept_kernel, dim3((D.nchains + 63) / 64), dim3(64), 0, st, D, keep_slot);
+    hipLaunchKernelGGL(accept_kernel, dim3((D.nchains + 63) / 64), dim3(64), 0, st, D, N, keep_slot);
     if (keep_slot >= 0)
         hipLaunchKernelGGL(keep_kernel, dim3(512), dim3(256), 0, st, D, keep_slot);
     return hipGetLastError();

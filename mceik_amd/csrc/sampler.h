@@ -11,6 +11,7 @@
 #include "block.h"
 #include "fsm_common.h"
 #include "hypo.h"
+#include "nuis.h"
 #include "posterior.h"
 #include "prior.h"
 
@@ -18,7 +19,7 @@
 #define MCEIK_MAX_PIPES 4
 #define MCEIK_ITERS_N (6 + MCEIK_TRAFFIC_N)   // d_iters: iterations, 4 visit statistics, solves, traffic
 
-// A pipe: a part of the chains stepped on a stream of its own.  D, B, P, H, fb
+// A pipe: a part of the chains stepped on a stream of its own.  D, B, P, H, N, fb
 // and fb_hyp are views of the sampler's restricted to the pipe's chains;
 // pipes_refresh alone writes them.
 struct Pipe {
@@ -26,6 +27,7 @@ struct Pipe {
     BlockDev B;
     PriorDev P;
     HypoDev H;
+    NuisDev N;
     mceik_fsm_batch fb;
     mceik_fsm_batch fb_hyp;            // a hypocentre step's batch (every model of the pipe's chains)
     void *ws;                          // the pipe's workspace: a part of the sampler's ws, ws itself, or its own
@@ -110,6 +112,21 @@ struct mceik_mcmc {
     int tt_interp;                     // trilinear mode (hypocentre moves are refused)
     unsigned long long *d_hcnt;        // [2][nev] attempts, accepts
     long long hyp_n;                   // states in the moments (cold chains x kept steps)
+    // Noise-scale and station-static moves (nuis.hip); off by
+    // default.  N.kn is null until an enable and again after a clear: while it
+    // is set the sampler holds nuisance state, every step takes the per-step
+    // branch, every logL honours the state, and a one-model sampler keeps its
+    // current tables too (D.ttab_cur = ttab_cur1, which the full forward then
+    // fills).  Global step gs is a nuisance step iff nuis_on and gs %
+    // nuis_every == nuis_offset and it is no hypocentre step.
+    bool nuis_on;
+    int nuis_every, nuis_offset;
+    NuisDev N;
+    NuisDev Nbuf;                      // the arrays of the first enable, kept across clear
+    int nuis_cap_sub, nuis_cap_nk;     // sub-moves / ladder entries the arrays hold
+    float *ttab_cur1;                  // one model: [nchains][nstat][nev] current tables while N.kn is set
+    long long nuis_n;                  // states in the moments (cold chains x kept steps)
+    std::vector<int> h_ostat, h_omask, h_ophase;   // [nobs] the observations' station, mask and phase (host copies)
     hipStream_t stream;
     void *ws;
     size_t ws_bytes;
@@ -141,6 +158,6 @@ int mcmc_forward_all(mceik_mcmc *s);
 int check_forward_ierr(mceik_mcmc *s, const char *who);
 int temper_cold(const mceik_mcmc *s);
 int temper_round(mceik_mcmc *s, int parity);
-// Recomputes every pipe's D, B, P and fb from the sampler's (and a multi-step
+// Recomputes every pipe's D, B, P, H, N and fb from the sampler's (and a multi-step
 // sampler's device copy of D): call after any change to s->D, s->B, s->P or s->fb.
 int pipes_refresh(mceik_mcmc *s);

@@ -4,7 +4,7 @@
 //
 // Host orchestration only.  The numerics live in fsm_kernel.hip,
 // fsm16_kernel.hip, mcmc_kernels.hip, temper.hip, block.hip, prior.hip,
-// hypo.hip and posterior.hip.
+// hypo.hip, nuis.hip and posterior.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -97,7 +97,7 @@ static int mcmc_forward(mceik_mcmc *s, bool timed, int k, const McmcExt *ext = n
 }
 
 // Untimed forward of every model of every chain (init, restore): tables into
-// ttab_cur (nphase 2) or the step tables (nphase 1).
+// ttab_cur (nphase 2, or nuisance state held) or the step tables (nphase 1).
 int mcmc_forward_all(mceik_mcmc *s)
 {
     if (mceik_fsm_batch_solve(&s->fb_all, s->ws, s->ws_bytes, s->stream)) return -1;
@@ -178,6 +178,18 @@ static HypoDev dev_view(const HypoDev &H, const McmcDev &D, int off)
     return V;
 }
 
+// The same view of the nuisance state's per-chain arrays (the tables, counters and moments are the sampler's).
+static NuisDev dev_view(const NuisDev &N, const McmcDev &D, int off)
+{
+    NuisDev V = N;
+    if (!N.kn) return V;
+    const size_t o = (size_t)off;
+    V.kn += o * D.nphase; V.kc += o * D.nphase * D.nstat;
+    V.var_eff += o * N.nobs; V.tcorr_eff += o * N.nobs;
+    V.rec += 4 * o * N.nsub; V.rlogl += 2 * o * N.nsub;
+    return V;
+}
+
 // Chains [off, off + n) of the hypocentre step's batch: nphase models per
 // chain.  It runs in the workspace of the pipe's step batch sb, so it keeps at
 // most that batch's resident waves (the workspace grows with the waves only).
@@ -226,6 +238,7 @@ int pipes_refresh(mceik_mcmc *s)
         p.P = dev_view(s->P, lo);
         p.fb = batch_view(s->fb, lo, n, (size_t)s->D.ncm);
         p.H = dev_view(s->H, s->D, lo);
+        p.N = dev_view(s->N, s->D, lo);
         if (s->H.hyp) p.fb_hyp = hyp_batch_view(s->fb_hyp, p.fb, lo, n, (size_t)s->D.ncm, s->D.nphase);
     }
     // the longest-first order covers the whole batch: one pipe's (mcmc_forward)
@@ -449,6 +462,8 @@ extern "C" int mceik_mcmc_init(const struct mceik_parms_struct *parms, const str
     memset(&s->B, 0, sizeof(s->B));
     s->B.ncx = ncx; s->B.ncy = ncy; s->B.ncz = ncz;
     memset(&s->P, 0, sizeof(s->P));
+    memset(&s->N, 0, sizeof(s->N));
+    memset(&s->Nbuf, 0, sizeof(s->Nbuf));
     // host-side problem tables
     std::vector<double> src((size_t)nstat * 4);
     for (int i = 0; i < nstat; i++) {
@@ -482,6 +497,8 @@ extern "C" int mceik_mcmc_init(const struct mceik_parms_struct *parms, const str
         const double *corr = sph ? st->scorr : st->pcorr;       // static corrections (mceik_struct.h:42-44)
         tcorr[j] = (use && corr) ? corr[k] : 0.0;
     }
+    s->h_ostat = ostat; s->h_omask = omask; s->h_ophase = ophase;
+    s->h_ostat.resize(nobs > 0 ? nobs : 0); s->h_omask.resize(nobs > 0 ? nobs : 0); s->h_ophase.resize(nobs > 0 ? nobs : 0);
     std::vector<float> sl((size_t)nch * ncm);
     for (size_t i = 0; i < sl.size(); i++) sl[i] = 1.0f / (float)v0[i];
     int rc = 0;
@@ -590,7 +607,7 @@ extern "C" int mceik_mcmc_init(const struct mceik_parms_struct *parms, const str
     b.solve_order = nullptr;
     s->fb_all.solve_clock = s->d_clock;
     s->fb_all.solve_order = nullptr;
-    if (mcmc_forward_all(s) || mcmc_init_loglik(D, s->stream) != hipSuccess ||
+    if (mcmc_forward_all(s) || mcmc_init_loglik(D, s->N, s->stream) != hipSuccess ||
         hipStreamSynchronize(s->stream) != hipSuccess) {
         mceik_mcmc_finalize(&s);
         return -1;
@@ -673,9 +690,9 @@ static bool swap_step(const mceik_mcmc *s, long long gs)
 
 int temper_round(mceik_mcmc *s, int parity)
 {
-    // (per-chain hypocentres travel with their models, enabled or not)
+    // (per-chain hypocentres and nuisance state travel with their models, enabled or not)
     HIPCHK(temper_swap_round(s->D, s->ntemps, parity, (uint64_t)s->step, s->d_tflag, s->d_tcnt,
-                             s->d_tcnt + s->D.nchains, s->stream, s->H.hyp ? &s->H : nullptr));
+                             s->d_tcnt + s->D.nchains, s->stream, s->H.hyp ? &s->H : nullptr, s->N.kn ? &s->N : nullptr));
     return 0;
 }
 
@@ -693,6 +710,21 @@ static hipError_t hypo_add(mceik_mcmc *s, const McmcDev &V, const HypoDev &H, in
     return hypo_moments(V, H, std::min(V.nchains, G - off), st);
 }
 
+// Global step gs runs the noise / statics sub-moves instead of proposing a
+// velocity (a step that is also a hypocentre step is a hypocentre step).
+static bool nuis_is_step(const mceik_mcmc *s, long long gs)
+{
+    return s->nuis_on && s->N.kn && s->nuis_every > 0 && gs % s->nuis_every == s->nuis_offset;
+}
+
+// The moments see the cold chains only, as the posterior does (post_add).
+static hipError_t nuis_add(mceik_mcmc *s, const McmcDev &V, const NuisDev &N, int off, hipStream_t st)
+{
+    const int G = temper_cold(s);
+    if (off >= G) return hipSuccess;
+    return nuis_moments(V, N, std::min(V.nchains, G - off), st);
+}
+
 // Steps of one call.  Returns -1 on a HIP failure; the caller joins the pipes
 // whatever happened, so the caller's stream is always ordered after every
 // kernel this call queued on the internal streams.
@@ -701,8 +733,9 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
     // block proposals: the multi-step kernel's epilogue is single-cell, so a
     // sampler built for multi-step launches (one pipe) steps per launch; the
     // prior's fold sits between a step's proposal and its forward, likewise;
-    // a hypocentre step has kernels and a batch of its own
-    if (s->persist && !s->block_on && !s->prior_on && !s->hypo_on) {
+    // a hypocentre step has kernels and a batch of its own; nuisance state
+    // enters every logL, which the multi-step kernel's epilogue does not know
+    if (s->persist && !s->block_on && !s->prior_on && !s->hypo_on && !s->N.kn) {
         // the first step's proposals here, then up to MCEIK_MC_CHUNK steps per
         // FSM launch (the kernel accepts, keeps and proposes the rest)
         for (int done = 0; done < nsteps;) {
@@ -738,6 +771,7 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
         int slot = -1;
         const bool post = s->post && kept_step(s, s->step);
         const bool hstep = hypo_step(s, s->step), hmom = s->hypo_on && kept_step(s, s->step);
+        const bool nstep = !hstep && nuis_is_step(s, s->step), nmom = s->nuis_on && s->N.kn && kept_step(s, s->step);
         if (s->max_samples && s->step >= s->nburn && (s->step - s->nburn) % s->keepk == 0) {
             slot = s->nkept % s->max_samples;
             s->nkept++;
@@ -761,19 +795,23 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
             if (hstep) {            // every event of every chain moves on one forward of the current models
                 HIPCHK(hypo_propose(p.D, p.H, step, st));
                 if (mcmc_forward(s, true, k, nullptr, true)) return -1;
-                HIPCHK(hypo_accept(p.D, p.H, slot, st));
+                HIPCHK(hypo_accept(p.D, p.H, p.N, slot, st));
+            } else if (nstep) {     // nsub sub-moves per chain from the tables the chain holds: no forward
+                HIPCHK(nuis_step(p.D, p.N, step, slot, st));
             } else {
                 HIPCHK(blk ? block_propose(p.D, p.B, step, st) : mcmc_propose(p.D, step, st));
                 if (s->prior_on) HIPCHK(prior_fold(p.D, p.B, p.P, blk, st));
                 if (mcmc_forward(s, true, k)) return -1;
-                HIPCHK(blk ? block_accept(p.D, p.B, slot, st) : mcmc_accept(p.D, slot, st));
+                HIPCHK(blk ? block_accept(p.D, p.B, p.N, slot, st) : mcmc_accept(p.D, p.N, slot, st));
             }
             if (post)               // the pipe's rows of the accumulators, offset like its keep_v (dev_view)
                 HIPCHK(post_add(s, p.D, p.D.chain_offset - s->D.chain_offset, st));
             if (hmom) HIPCHK(hypo_add(s, p.D, p.H, p.D.chain_offset - s->D.chain_offset, st));
+            if (nmom) HIPCHK(nuis_add(s, p.D, p.N, p.D.chain_offset - s->D.chain_offset, st));
         }
         if (post) mcmc_post_counted(s->post);
         if (hmom) s->hyp_n += temper_cold(s);
+        if (nmom) s->nuis_n += temper_cold(s);
         if (s->report) clock_report(s, "step");
         s->step++;
     }

@@ -1,6 +1,7 @@
 // sampler_api.hip -- the sampler's accessors of the C-ABI (include/mceik.h:
 // sync, state, checkpoint / restore, kept samples, info, FSM statistics) and
-// its parallel-tempering, block-proposal, prior and hypocentre entry points.
+// its parallel-tempering, block-proposal, prior, hypocentre and noise / statics
+// entry points.
 // The sampler itself is sampler.hip.
 #include <hip/hip_runtime.h>
 #include <float.h>
@@ -8,6 +9,7 @@
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -518,6 +520,284 @@ extern "C" int mceik_hypo_draw(uint32_t seed, uint32_t gchain, uint64_t step, in
     return 0;
 }
 
+// ---------------------------------------------------------------------------
+// noise-scale and station-static moves (include/mceik.h mceik_mcmc_nuis_*)
+
+static size_t nuis_npar(const McmcDev &D) { return (size_t)D.nphase + (size_t)D.nphase * D.nstat; }
+static size_t nuis_nmom(const McmcDev &D, int nk) { return 2 * (size_t)D.nphase + (size_t)D.nphase * nk + 2 * (size_t)D.nphase * D.nstat; }
+
+// Every ladder index inside [0, nk) and every static inside [-kcmax, kcmax].
+static bool nuis_state_ok(const McmcDev &D, const int *kn, const int *kc, int nk, int kcmax)
+{
+    const size_t nn = (size_t)D.nchains * D.nphase, nc = nn * D.nstat;
+    for (size_t i = 0; i < nn; i++) if (kn[i] < 0 || kn[i] >= nk) return false;
+    for (size_t i = 0; i < nc; i++) if (kc[i] < -kcmax || kc[i] > kcmax) return false;
+    return true;
+}
+
+extern "C" int mceik_mcmc_nuis_enable(mceik_mcmc *s, const mceik_nuis_opts *o)
+{
+    if (!s || !o) return 1;
+    McmcDev &D = s->D;
+    const int nph = D.nphase, nst = D.nstat, nch = D.nchains, nobs = (int)s->h_ostat.size();
+    const bool noise = o->noise != 0, statics = o->statics != 0;
+    if (!noise && !statics) return 1;
+    if (o->every <= 0 || o->offset < 0 || o->offset >= o->every || o->nsub <= 0) return 1;
+    if (o->dk < 0 || o->dc < 0 || o->kcmax < 0 || o->dc > 0x3fffffff || o->kcmax > 0x3fffffff) return 1;
+    if (statics && !(o->dt > 0.0 && o->dt <= DBL_MAX)) return 1;
+    // the ladder: an odd number of entries, the middle one the start value (1, 0) exactly; statics alone need none
+    static const double one = 1.0, zero = 0.0;
+    const bool own = !noise && !o->lam && !o->lnlam;
+    const int nk = own ? 1 : o->nk;
+    const double *lam = own ? &one : o->lam, *lnlam = own ? &zero : o->lnlam;
+    if (nk < 1 || nk % 2 == 0 || !lam || !lnlam || lam[nk / 2] != 1.0 || lnlam[nk / 2] != 0.0) return 1;
+    for (int k = 0; k < nk; k++)
+        if (!(lam[k] > 0.0 && lam[k] <= DBL_MAX) || !(fabs(lnlam[k]) <= DBL_MAX)) return 1;
+    // the stations statics moves draw from: those with a used pick of the phase, in station order
+    std::vector<int> act((size_t)nph * nst, 0);
+    int nact[2] = {0, 0};
+    double norm[2] = {0.0, 0.0};
+    {
+        std::vector<unsigned char> has((size_t)nph * nst, 0);
+        for (int j = 0; j < nobs; j++)
+            if (!s->h_omask[j]) {
+                has[(size_t)s->h_ophase[j] * nst + s->h_ostat[j]] = 1;
+                norm[s->h_ophase[j]] += 1.0;
+            }
+        for (int ph = 0; ph < nph; ph++)
+            for (int k = 0; k < nst; k++)
+                if (has[(size_t)ph * nst + k]) act[(size_t)ph * nst + nact[ph]++] = k;
+    }
+    for (int ph = 0; ph < 2; ph++) {
+        if (!statics || nact[ph] < 2) nact[ph] = 0;         // a pair needs two stations
+        if (o->norm && ph < nph) norm[ph] = o->norm[ph];
+        if (!(fabs(norm[ph]) <= DBL_MAX)) return 1;
+    }
+    if ((noise ? nph : 0) + nact[0] + nact[1] == 0) return 1;
+    if (s->post && mcmc_post_count(s->post) > 0) return 1;
+    // MCEIK_NUIS_LDS (test hook): fewer bytes of LDS for a nuisance step's block, so that small problems take
+    // the path without the staged travel times
+    size_t lds_max = MCEIK_NUIS_LDS_MAX;
+    if (const char *lds_env = getenv("MCEIK_NUIS_LDS")) lds_max = std::min<size_t>(lds_max, strtoul(lds_env, nullptr, 10));
+    NuisDev T;
+    memset(&T, 0, sizeof(T));
+    T.nobs = nobs;
+    if (nuis_lds_bytes(D, T, false) > lds_max) {
+        fprintf(stderr, "mceik_mcmc_nuis_enable: 8 nev + 4 nphase nstat = %zu B exceed the %zu B of LDS a nuisance step "
+                        "uses\n", nuis_lds_bytes(D, T, false), lds_max);
+        return 1;
+    }
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    const size_t nn = (size_t)nch * nph, nc = nn * nst;
+    if (s->N.kn) {
+        // state is held: its indices keep their meaning on a ladder of the same length only, its statics in the new box
+        std::vector<int> kn(nn), kc(nc);
+        HIPCHK(hipMemcpy(kn.data(), s->N.kn, nn * sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(kc.data(), s->N.kc, nc * sizeof(int), hipMemcpyDeviceToHost));
+        if (nk != s->N.nk || !nuis_state_ok(D, kn.data(), kc.data(), nk, statics ? o->kcmax : 0x3fffffff)) return 1;
+    }
+    NuisDev &B = s->Nbuf;
+    if (!B.kn) {                       // every array or none: a failed enable leaves the sampler as it was
+        NuisDev A;
+        memset(&A, 0, sizeof(A));
+        unsigned long long *cnt = nullptr;
+        int *dact = nullptr;
+        float *tc1 = nullptr;
+        if (dalloc(s, &A.kn, nn) || dalloc(s, &A.kc, nc) || dalloc(s, &A.var_eff, (size_t)nch * nobs) ||
+            dalloc(s, &A.tcorr_eff, (size_t)nch * nobs) || dalloc(s, &cnt, 2 * nuis_npar(D)) || dalloc(s, &dact, (size_t)nph * nst) ||
+            (nph == 1 && dalloc(s, &tc1, (size_t)nch * nst * D.nev)))
+            return -1;
+        A.attempts = cnt;
+        A.accepts = cnt + nuis_npar(D);
+        A.act = dact;
+        A.var0 = D.var;
+        A.tcorr0 = D.tcorr;
+        A.nobs = nobs;
+        B = A;
+        s->ttab_cur1 = tc1;
+    }
+    if (o->nsub > s->nuis_cap_sub) {
+        int *rec = nullptr;
+        double *rl = nullptr;
+        if (dalloc(s, &rec, 4 * (size_t)nch * o->nsub) || dalloc(s, &rl, 2 * (size_t)nch * o->nsub)) return -1;
+        B.rec = rec;
+        B.rlogl = rl;
+        s->nuis_cap_sub = o->nsub;
+    }
+    if (nk > s->nuis_cap_nk) {
+        double *tab = nullptr;
+        long long *mom = nullptr;
+        if (dalloc(s, &tab, 2 * (size_t)nk) || dalloc(s, &mom, nuis_nmom(D, nk))) return -1;
+        B.lam = tab;
+        B.lnlam = tab + nk;
+        B.mom = mom;
+        s->nuis_cap_nk = nk;
+    }
+    HIPCHK(hipMemcpy((void *)B.lam, lam, (size_t)nk * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy((void *)B.lnlam, lnlam, (size_t)nk * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy((void *)B.act, act.data(), act.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(B.attempts, 0, 2 * nuis_npar(D) * 8));
+    HIPCHK(hipMemset(B.mom, 0, nuis_nmom(D, nk) * 8));
+    HIPCHK(hipMemset(B.rec, 0, 4 * (size_t)nch * o->nsub * sizeof(int)));
+    HIPCHK(hipMemset(B.rlogl, 0, 2 * (size_t)nch * o->nsub * 8));
+    if (!s->N.kn) {                    // the start values: the ladder's middle entry, no static
+        std::vector<int> kn(nn, nk / 2);
+        HIPCHK(hipMemcpy(B.kn, kn.data(), nn * sizeof(int), hipMemcpyHostToDevice));
+        HIPCHK(hipMemset(B.kc, 0, nc * sizeof(int)));
+    }
+    B.nk = nk; B.dk = o->dk; B.dc = o->dc; B.nsub = o->nsub;
+    B.noise_on = noise; B.statics_on = statics;
+    B.lds_te = nuis_lds_bytes(D, B, true) <= lds_max;
+    B.nact0 = nact[0]; B.nact1 = nact[1];
+    if (statics) { B.kcmax = o->kcmax; B.dt = o->dt; }
+    else if (!s->N.kn) { B.kcmax = 0; B.dt = 0.0; }        // (statics held from an earlier enable keep their dt)
+    B.norm0 = norm[0]; B.norm1 = norm[1];
+    s->N = B;
+    s->nuis_n = 0;
+    s->nuis_every = o->every;
+    s->nuis_offset = o->offset;
+    s->nuis_on = true;
+    if (nph == 1) {                    // a one-model sampler keeps its current tables while the state is held
+        D.ttab_cur = s->ttab_cur1;
+        s->fb_all.ttab = s->ttab_cur1;
+    }
+    if (pipes_refresh(s)) return -1;
+    HIPCHK(nuis_rows(D, s->N, s->stream));
+    return forward_logl(s, "mceik_mcmc_nuis_enable");       // fills the current tables; logL with the state
+}
+
+extern "C" int mceik_mcmc_nuis_disable(mceik_mcmc *s)
+{
+    if (!s) return 1;
+    s->nuis_on = false;                // host state only: the values stay and every logL keeps honouring them
+    return 0;
+}
+
+extern "C" int mceik_mcmc_nuis_clear(mceik_mcmc *s)
+{
+    if (!s) return 1;
+    if (!s->N.kn) return 0;
+    if (s->post && mcmc_post_count(s->post) > 0) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    s->nuis_on = false;
+    memset(&s->N, 0, sizeof(s->N));
+    if (s->D.nphase == 1) {
+        s->D.ttab_cur = nullptr;
+        s->fb_all.ttab = s->fb.ttab;
+    }
+    if (pipes_refresh(s)) return -1;
+    return forward_logl(s, "mceik_mcmc_nuis_clear");
+}
+
+extern "C" int mceik_mcmc_nuis_get(mceik_mcmc *s, mceik_nuis_opts *o, double *lam, double *lnlam, double *norm, int *kn,
+                                   int *kc)
+{
+    if (!s || !s->N.kn) return 1;
+    const NuisDev &N = s->N;
+    const McmcDev &D = s->D;
+    if (o) {
+        memset(o, 0, sizeof(*o));
+        o->every = s->nuis_on ? s->nuis_every : 0;
+        o->offset = s->nuis_offset; o->nsub = N.nsub;
+        o->noise = N.noise_on; o->statics = N.statics_on;
+        o->nk = N.nk; o->dk = N.dk; o->dc = N.dc; o->kcmax = N.kcmax; o->dt = N.dt;
+    }
+    if (norm) {
+        norm[0] = N.norm0;
+        if (D.nphase > 1) norm[1] = N.norm1;
+    }
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    const size_t nn = (size_t)D.nchains * D.nphase;
+    if (lam) HIPCHK(hipMemcpy(lam, N.lam, (size_t)N.nk * 8, hipMemcpyDeviceToHost));
+    if (lnlam) HIPCHK(hipMemcpy(lnlam, N.lnlam, (size_t)N.nk * 8, hipMemcpyDeviceToHost));
+    if (kn) HIPCHK(hipMemcpy(kn, N.kn, nn * sizeof(int), hipMemcpyDeviceToHost));
+    if (kc) HIPCHK(hipMemcpy(kc, N.kc, nn * D.nstat * sizeof(int), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int mceik_mcmc_nuis_set(mceik_mcmc *s, const int *kn, const int *kc)
+{
+    if (!s || !s->N.kn || !kn || !kc) return 1;
+    const NuisDev &N = s->N;
+    const McmcDev &D = s->D;
+    if (!nuis_state_ok(D, kn, kc, N.nk, N.kcmax)) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    const size_t nn = (size_t)D.nchains * D.nphase;
+    HIPCHK(hipMemcpy(N.kn, kn, nn * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(N.kc, kc, nn * D.nstat * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(nuis_rows(D, N, s->stream));
+    HIPCHK(mcmc_init_loglik(D, N, s->stream));          // from the kept current tables: no solve
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return 0;
+}
+
+extern "C" int mceik_mcmc_nuis_stats(mceik_mcmc *s, long long *attempts, long long *accepts, int reset)
+{
+    if (!s || !s->N.kn) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    const size_t n = nuis_npar(s->D) * 8;
+    if (attempts) HIPCHK(hipMemcpy(attempts, s->N.attempts, n, hipMemcpyDeviceToHost));
+    if (accepts) HIPCHK(hipMemcpy(accepts, s->N.accepts, n, hipMemcpyDeviceToHost));
+    if (reset) HIPCHK(hipMemset(s->N.attempts, 0, 2 * n));
+    return 0;
+}
+
+extern "C" int mceik_mcmc_nuis_last(mceik_mcmc *s, int *rec, double *logl)
+{
+    if (!s || !s->N.kn) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    const size_t n = (size_t)s->D.nchains * s->N.nsub;
+    if (rec) HIPCHK(hipMemcpy(rec, s->N.rec, 4 * n * sizeof(int), hipMemcpyDeviceToHost));
+    if (logl) HIPCHK(hipMemcpy(logl, s->N.rlogl, 2 * n * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int mceik_mcmc_nuis_moments_get(mceik_mcmc *s, long long *n, long long *ksum, long long *hist, long long *csum)
+{
+    if (!s || !s->N.kn) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    const McmcDev &D = s->D;
+    const size_t a = 2 * (size_t)D.nphase, b = (size_t)D.nphase * s->N.nk, c = 2 * (size_t)D.nphase * D.nstat;
+    if (n) *n = s->nuis_n;
+    if (ksum) HIPCHK(hipMemcpy(ksum, s->N.mom, a * 8, hipMemcpyDeviceToHost));
+    if (hist) HIPCHK(hipMemcpy(hist, s->N.mom + a, b * 8, hipMemcpyDeviceToHost));
+    if (csum) HIPCHK(hipMemcpy(csum, s->N.mom + a + b, c * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int mceik_mcmc_nuis_moments_set(mceik_mcmc *s, long long n, const long long *ksum, const long long *hist,
+                                           const long long *csum)
+{
+    if (!s || !s->N.kn || n < 0 || !ksum || !hist || !csum) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    const McmcDev &D = s->D;
+    const size_t a = 2 * (size_t)D.nphase, b = (size_t)D.nphase * s->N.nk, c = 2 * (size_t)D.nphase * D.nstat;
+    HIPCHK(hipMemcpy(s->N.mom, ksum, a * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s->N.mom + a, hist, b * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s->N.mom + a + b, csum, c * 8, hipMemcpyHostToDevice));
+    s->nuis_n = n;
+    return 0;
+}
+
+extern "C" int mceik_nuis_draw(uint32_t seed, uint32_t gchain, uint64_t step, int sub, int nnoise, int nact0, int nact1,
+                               int dk, int dc, int m[5], double *logu)
+{
+    if (sub < 0 || !m || nnoise < 0 || nnoise > 2 || nact0 < 0 || nact1 < 0 || nact0 == 1 || nact1 == 1 || dk < 0 ||
+        dc < 0 || dc > 0x3fffffff || (long long)nnoise + nact0 + nact1 < 1 || (long long)nnoise + nact0 + nact1 > INT_MAX)
+        return 1;
+    const uint32_t r3 = nuis_draw(seed, gchain, step, sub, nnoise, nact0, nact1, dk, dc, m);
+    if (logu) *logu = hypo_det_log_host(((double)r3 + 0.5) * (1.0 / 4294967296.0));
+    return 0;
+}
+
 int mcmc_post_ctx(mceik_mcmc *s, McmcPostCtx *out)
 {
     if (!s || !out) return 1;
@@ -583,7 +863,7 @@ static int forward_logl(mceik_mcmc *s, const char *who)
     unsigned long long keep[MCEIK_ITERS_N];
     HIPCHK(hipMemcpy(keep, s->d_iters, sizeof(keep), hipMemcpyDeviceToHost));
     if (mcmc_forward_all(s)) return -1;
-    HIPCHK(mcmc_init_loglik(s->D, s->stream));
+    HIPCHK(mcmc_init_loglik(s->D, s->N, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
     HIPCHK(hipMemcpy(s->d_iters, keep, sizeof(keep), hipMemcpyHostToDevice));
     return check_forward_ierr(s, who) ? 2 : 0;
@@ -702,8 +982,8 @@ extern "C" int mceik_mcmc_get_info(mceik_mcmc *s, mceik_mcmc_info *info)
     DeviceScope dg(s->device);
     memset(info, 0, sizeof(*info));
     info->npipe = s->npipe;
-    // block proposals, the prior and hypocentre moves step per launch
-    info->multi_step = s->persist && !s->block_on && !s->prior_on && !s->hypo_on ? 1 : 0;
+    // block proposals, the prior, hypocentre moves and nuisance state step per launch
+    info->multi_step = s->persist && !s->block_on && !s->prior_on && !s->hypo_on && !s->N.kn ? 1 : 0;
     info->nphase = s->D.nphase;
     info->masked_s = s->masked_s;
     FsmLaunch L;

@@ -6,6 +6,7 @@
 
 #include "hypo.h"
 #include "mcmc_common.h"
+#include "nuis.h"
 
 // One swap round of the whole sampler (D is the sampler's state, never a
 // pipe's view; D.beta set) on stream st: the decide kernel, then the exchange
@@ -14,7 +15,9 @@
 // parity sit the round out.  gs is the Philox counter (the global step the
 // round belongs to).  flag: [(ntemps - 1) * G] ints of scratch; attempts,
 // accepts: [ntemps - 1] counters.  H (or null): the chains' hypocentres and
-// event lists, exchanged with the models.  No host synchronisation.
+// event lists, N (or null) their nuisance state (kn, kc and the effective
+// rows), exchanged with the models; the current tables wherever the sampler
+// keeps them (D.ttab_cur).  No host synchronisation.
 hipError_t temper_swap_round(const McmcDev &D, int ntemps, int parity, uint64_t gs, int *flag,
                              unsigned long long *attempts, unsigned long long *accepts, hipStream_t st,
-                             const HypoDev *H = nullptr);
+                             const HypoDev *H = nullptr, const NuisDev *N = nullptr);

@@ -125,16 +125,16 @@ __global__ __launch_bounds__(TEMPER_BLOCK) void temper_exchange_kernel(TemperRow
 
 hipError_t temper_swap_round(const McmcDev &D, int ntemps, int parity, uint64_t gs, int *flag,
                              unsigned long long *attempts, unsigned long long *accepts, hipStream_t st,
-                             const HypoDev *H)
+                             const HypoDev *H, const NuisDev *N)
 {
     if (ntemps < 2 || !D.beta) return hipSuccess;
     const int G = D.nchains / ntemps, npairs = (ntemps - 1) * G;
     if (npairs <= 0) return hipSuccess;
     hipLaunchKernelGGL(temper_decide_kernel, dim3((npairs + 63) / 64), dim3(64), 0, st, D, G, npairs, parity, gs, flag,
                        attempts, accepts);
-    // v, slow_cur and slow_prop rows of ncm entries; with two models the current tables
+    // v, slow_cur and slow_prop rows of ncm entries; the current tables where the sampler keeps them
     const int nt = (D.ncm + TEMPER_TILE - 1) / TEMPER_TILE;
-    const int ltab = D.nphase > 1 && D.ttab_cur ? D.nphase * D.nstat * D.nev : 0;
+    const int ltab = D.ttab_cur ? D.nphase * D.nstat * D.nev : 0;
     TemperRows R;
     R.p0 = (unsigned *)D.v; R.p1 = (unsigned *)D.slow_cur; R.p2 = (unsigned *)D.slow_prop; R.p3 = (unsigned *)D.ttab_cur;
     R.len0 = R.len1 = R.len2 = D.ncm;
@@ -152,6 +152,19 @@ hipError_t temper_swap_round(const McmcDev &D, int ntemps, int parity, uint64_t 
         Q.p0 = (unsigned *)H->hyp; Q.p1 = (unsigned *)H->ev1; Q.p2 = (unsigned *)H->evall; Q.p3 = nullptr;
         Q.len0 = 3 * D.nev; Q.len1 = D.nev; Q.len2 = H->evall ? D.nphase * D.nev : 0; Q.len3 = 0;
         Q.t1 = tiles(Q.len0); Q.t2 = Q.t1 + tiles(Q.len1); Q.t3 = Q.t2 + tiles(Q.len2); Q.t4 = Q.t3;
+        for (int p0 = 0; p0 < npairs; p0 += TEMPER_MAX_GRID_Y) {
+            const int np = npairs - p0 < TEMPER_MAX_GRID_Y ? npairs - p0 : TEMPER_MAX_GRID_Y;
+            hipLaunchKernelGGL(temper_exchange_kernel, dim3(Q.t4, np), dim3(TEMPER_BLOCK), 0, st, Q, flag, p0, G);
+        }
+    }
+    if (N && N->kn) {
+        // the ladder indices, the statics and the effective rows (nuis.h): rows of nphase and nphase * nstat
+        // ints and of nobs doubles
+        auto tiles = [](int len) { return (len + TEMPER_TILE - 1) / TEMPER_TILE; };
+        TemperRows Q;
+        Q.p0 = (unsigned *)N->kn; Q.p1 = (unsigned *)N->kc; Q.p2 = (unsigned *)N->var_eff; Q.p3 = (unsigned *)N->tcorr_eff;
+        Q.len0 = D.nphase; Q.len1 = D.nphase * D.nstat; Q.len2 = Q.len3 = 2 * N->nobs;
+        Q.t1 = tiles(Q.len0); Q.t2 = Q.t1 + tiles(Q.len1); Q.t3 = Q.t2 + tiles(Q.len2); Q.t4 = Q.t3 + tiles(Q.len3);
         for (int p0 = 0; p0 < npairs; p0 += TEMPER_MAX_GRID_Y) {
             const int np = npairs - p0 < TEMPER_MAX_GRID_Y ? npairs - p0 : TEMPER_MAX_GRID_Y;
             hipLaunchKernelGGL(temper_exchange_kernel, dim3(Q.t4, np), dim3(TEMPER_BLOCK), 0, st, Q, flag, p0, G);

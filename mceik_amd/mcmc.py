@@ -414,6 +414,52 @@ def hypo_draw(seed, gchain, step, e, dmax=(1, 1, 1)):
     return d, logu.value
 
 
+def nuis_ladder(nk, lam_min, lam_max):
+    """(lam, lnlam) float64 [nk]: a log-uniform noise ladder from lam_min to
+    lam_max for `Sampler.nuis_enable`, lnlam[k] = (k - nk // 2) * ln(lam_max) /
+    (nk // 2) and lam = exp(lnlam), so that the middle entry -- the chains'
+    start value -- is exactly lam = 1.0, lnlam = 0.0.  nk is odd and lam_min is
+    1 / lam_max (None: that): equal steps in ln lam on both sides of 1 are what
+    makes a uniform prior on the index a log-uniform prior on the scale."""
+    nk, lam_max = int(nk), float(lam_max)
+    if nk < 1 or nk % 2 == 0:
+        raise ValueError("nuis_ladder: nk is odd (the middle entry is the start value lam = 1)")
+    if not (lam_max >= 1.0 and np.isfinite(lam_max)):
+        raise ValueError("nuis_ladder: a finite lam_max >= 1")
+    if lam_min is not None and not np.isclose(float(lam_min) * lam_max, 1.0, rtol=1e-12, atol=0.0):
+        raise ValueError("nuis_ladder: lam_min is 1 / lam_max (a ladder with equal steps in ln lam around lam = 1)")
+    mid = nk // 2
+    lnlam = np.array([(k - mid) * (np.log(lam_max) / mid) if mid else 0.0 for k in range(nk)], np.float64)
+    lam = np.exp(lnlam)
+    lam[mid], lnlam[mid] = 1.0, 0.0
+    return lam, lnlam
+
+
+def nuis_active(p):
+    """int32 [nphase] lists of the stations statics moves draw from: those with
+    a used pick of the phase, in station order (`Sampler.nuis_enable`)."""
+    used, ph = p.obs_mask == 0, p.obs_phase
+    return [np.unique(p.obs_stat[used & (ph == q)]).astype(np.int32) for q in range(p.nphase)]
+
+
+def nuis_draw(seed, gchain, step, sub, nnoise, nact, dk=1, dc=1):
+    """Sub-move `sub` of global chain `gchain` at global step `step`
+    (mceik_nuis_draw; host only): ((kind, phase, a, b, delta), log u) with kind
+    0 a noise move of `phase` by delta ladder entries, kind 1 a statics move of
+    the a-th and b-th active stations of `phase` by +delta and -delta units.
+    nnoise = nphase with the noise part on, else 0; nact = active stations per
+    phase that the statics part draws from (0 or >= 2 each)."""
+    na = [int(x) for x in np.ravel(nact)] + [0]
+    if len(na) > 3:
+        raise ValueError("nuis_draw: nact is one count per phase")
+    m, logu = np.zeros(5, np.int32), C.c_double(0.0)
+    rc = _lib.lib().mceik_nuis_draw(int(seed), int(gchain), int(step), int(sub), int(nnoise), na[0], na[1], int(dk),
+                                    int(dc), m.ctypes.data_as(C.c_void_p), C.byref(logu))
+    if rc != 0:
+        raise ValueError("nuis_draw: sub >= 0, nnoise in [0, 2], every nact 0 or >= 2, something to move, dk, dc >= 0")
+    return tuple(int(x) for x in m), logu.value
+
+
 def prior_weight(sigma):
     """w = 1 / (2 sigma^2) per phase from a sigma in m/s: a scalar (both
     phases) or a (P, S) pair; None is weight 0."""
@@ -432,6 +478,15 @@ def prior_weight(sigma):
             raise ValueError("a sigma is positive and finite (None: weight 0)")
         out.append(1.0 / (2.0 * s * s))
     return tuple(out)
+
+
+def _nuis_same(a, b):
+    """Two option dicts of `Sampler.nuis_enable` describe the same moves."""
+    def eq(x, y):
+        if x is None or y is None:
+            return x is None and y is None
+        return np.asarray(x, np.float64).tobytes() == np.asarray(y, np.float64).tobytes()
+    return set(a) == set(b) and all(eq(a[k], b[k]) for k in a)
 
 
 class Sampler:
@@ -473,6 +528,8 @@ class Sampler:
         self._prior = None              # (w_smooth, w_damp, vref digest) while the prior is enabled
         self._hypo = None               # (every, dmax, lo, hi) while hypocentre moves are enabled
         self._hypo_base = None          # (attempts, accepts) of a restored checkpoint, as _temper_base
+        self._nuis = None               # the options while the sampler holds nuisance state (nuis_enable .. nuis_clear)
+        self._nuis_base = None          # (attempts, accepts) of a restored checkpoint, as _temper_base
 
     @property
     def model_shape(self):
@@ -576,6 +633,11 @@ class Sampler:
             n, sm, sq = self._hypo_moments()
             ck["hypo"] = {"every": self._hypo[0], "dmax": self._hypo[1], "lo": self._hypo[2], "hi": self._hypo[3],
                           "xyz": self.hypo_positions(), "attempts": att, "accepts": acc, "n": n, "sum": sm, "sq": sq}
+        if self._nuis is not None:       # the values are chain state; the options decide what is proposed
+            att, acc = self.nuis_stats()
+            kn, kc = self.nuis_get()
+            ck["nuis"] = {"opts": dict(self._nuis), "kn": kn, "kc": kc, "attempts": att, "accepts": acc,
+                          "moments": self.nuis_moments()}
         return ck
 
     def restore(self, ck, recompute_logl=False):
@@ -600,6 +662,14 @@ class Sampler:
             if self._hypo is None or (int(hk["every"]), tuple(hk["dmax"]), tuple(hk["lo"]), tuple(hk["hi"])) != self._hypo:
                 raise ValueError("the checkpoint was taken with other hypocentre-move options")
             self.hypo_set(hk["xyz"])     # (its forward is at the old models: the restore below sets logL)
+        nk = ck.get("nuis")              # likewise; held values need the forward of the restore: it makes the
+        if nk is not None:               # current tables every later nuisance step reads (and gives the saved logL)
+            if self._nuis is None or not _nuis_same(nk["opts"], self._nuis):
+                raise ValueError("the checkpoint was taken with other noise / statics options")
+            self.nuis_set(nk["kn"], nk["kc"])
+            recompute_logl = True
+        elif self._nuis is not None:
+            recompute_logl = True
         v = np.ascontiguousarray(ck["v"], dtype=np.int32)
         assert v.shape == self.model_shape
         logl = None if recompute_logl else np.ascontiguousarray(ck["logl"], dtype=np.float64)
@@ -629,6 +699,10 @@ class Sampler:
                                                      sq.ctypes.data_as(C.c_void_p))
             if rc != 0:
                 raise RuntimeError(f"mceik_mcmc_hypo_moments_set failed ({rc})")
+        if nk is not None:
+            self.nuis_stats(reset=True)
+            self._nuis_base = (np.asarray(nk["attempts"], np.int64).copy(), np.asarray(nk["accepts"], np.int64).copy())
+            self.nuis_moments_set(nk["moments"])
 
     # --- streaming posterior (include/mceik.h mceik_mcmc_posterior_*) ---
     def posterior_enable(self, per_chain=True, nbins=64):
@@ -976,6 +1050,179 @@ class Sampler:
             second[:, a, b] = second[:, b, a] = sq[:, k] / n
         cov = (second - mu[:, :, None] * mu[:, None, :]) * (p.h * p.h)
         return np.array([p.x0, p.y0, p.z0]) + p.h * mu, cov
+
+    # --- noise scale and station statics (include/mceik.h mceik_mcmc_nuis_*) ---
+    def nuis_enable(self, every, offset=0, nsub=16, ladder=None, dk=1, statics_dt=None, dc=1, kcmax=0, norm=None):
+        """Sample the noise scale and / or the station statics with the velocity
+        models.  `ladder` = (lam, lnlam) from `nuis_ladder`
+        turns the noise part on: every chain scales var of phase ph by
+        lam[kn[ph]], a move is +-[1, max(dk, 1)] ladder entries.  `statics_dt`
+        (seconds) turns the statics part on: every chain adds kc * statics_dt
+        to the static of each (phase, station), |kc| <= kcmax, a move shifts a
+        zero-sum pair of stations by +-[1, max(dc, 1)] units.  Global step gs
+        is a nuisance step iff gs % every == offset: `nsub` sub-moves per chain
+        from the tables the chain holds, no eikonal solve.  `norm` [nphase]
+        weighs the noise normalisation (None: the used picks per phase).  The
+        values start at lam = 1 and kc = 0, where every logL is the plain
+        sampler's; they stay across `nuis_disable` and a second enable, until
+        `nuis_clear`.  While they are held every step is one launch
+        (`info()["multi_step"]` is False).  Resets the counters and the moments."""
+        p = self.p
+        o = _lib.NuisOpts()
+        o.every, o.offset, o.nsub = int(every), int(offset), int(nsub)
+        o.noise, o.statics = int(ladder is not None), int(statics_dt is not None)
+        keep = []
+        lam = lnlam = None
+        if ladder is not None:
+            lam, lnlam = (np.ascontiguousarray(a, dtype=np.float64).ravel() for a in ladder)
+            if lam.size != lnlam.size:
+                raise ValueError("nuis_enable: lam and lnlam are one ladder")
+            o.nk, o.lam, o.lnlam = lam.size, lam.ctypes.data, lnlam.ctypes.data
+            keep += [lam, lnlam]
+        o.dk, o.dc, o.kcmax = int(dk), int(dc), int(kcmax)
+        o.dt = float(statics_dt) if statics_dt is not None else 0.0
+        if norm is not None:
+            nm = np.ascontiguousarray(norm, dtype=np.float64).ravel()
+            if nm.size != p.nphase:
+                raise ValueError("nuis_enable: norm is one weight per phase")
+            o.norm = nm.ctypes.data
+            keep.append(nm)
+        rc = self._L.mceik_mcmc_nuis_enable(self._h, C.byref(o))
+        if rc != 0:
+            raise (ValueError if rc == 1 else RuntimeError)(
+                f"mceik_mcmc_nuis_enable failed ({rc}): a ladder or statics_dt > 0, every > 0, 0 <= offset < every, "
+                "nsub > 0, an odd ladder with the middle entry (1, 0), dk, dc, kcmax >= 0, something to move, held "
+                "values that fit, and no states in an enabled posterior")
+        self._nuis = {"every": int(every), "offset": int(offset), "nsub": int(nsub), "dk": int(dk), "dc": int(dc),
+                      "kcmax": int(kcmax) if statics_dt is not None else None,
+                      "dt": float(statics_dt) if statics_dt is not None else None,
+                      "lam": None if lam is None else lam.copy(), "lnlam": None if lnlam is None else lnlam.copy(),
+                      "norm": None if norm is None else nm.copy()}
+        self._nuis_base = None
+        self._last_full = True
+
+    def nuis_disable(self):
+        """Later steps are velocity (and hypocentre) steps again; the values stay
+        and every logL keeps honouring them."""
+        if self._L.mceik_mcmc_nuis_disable(self._h) != 0:
+            raise RuntimeError("mceik_mcmc_nuis_disable failed")
+        if self._nuis is not None:
+            self._nuis = dict(self._nuis, every=0)
+
+    def nuis_clear(self):
+        """Every chain back to lam = 1 and kc = 0, logL recomputed: the plain
+        sampler again, multi-step launches included."""
+        rc = self._L.mceik_mcmc_nuis_clear(self._h)
+        if rc != 0:
+            raise (ValueError if rc == 1 else RuntimeError)(f"mceik_mcmc_nuis_clear failed ({rc})")
+        self._nuis = None
+        self._nuis_base = None
+        self._last_full = True
+
+    def _nuis_held(self, rc, what):
+        if rc != 0:
+            raise RuntimeError(f"{what} failed ({rc}): the sampler holds no noise / statics values (nuis_enable)")
+
+    def nuis_get(self):
+        """(kn int32 [nchains, nphase], kc int32 [nchains, nphase, nstat]): every
+        chain's ladder index per phase and static per (phase, station) in units."""
+        p = self.p
+        kn, kc = np.empty((self.nchains, p.nphase), np.int32), np.empty((self.nchains, p.nphase, p.nstat), np.int32)
+        self._nuis_held(self._L.mceik_mcmc_nuis_get(self._h, None, None, None, None, kn.ctypes.data_as(C.c_void_p),
+                                                    kc.ctypes.data_as(C.c_void_p)), "mceik_mcmc_nuis_get")
+        return kn, kc
+
+    def nuis_options(self):
+        """The options in force as the library holds them: a dict with the
+        ladder, norm and every (0 after `nuis_disable`)."""
+        o = _lib.NuisOpts()
+        self._nuis_held(self._L.mceik_mcmc_nuis_get(self._h, C.byref(o), None, None, None, None, None),
+                        "mceik_mcmc_nuis_get")
+        lam, lnlam, norm = np.empty(o.nk), np.empty(o.nk), np.empty(self.p.nphase)
+        self._L.mceik_mcmc_nuis_get(self._h, None, lam.ctypes.data_as(C.c_void_p), lnlam.ctypes.data_as(C.c_void_p),
+                                    norm.ctypes.data_as(C.c_void_p), None, None)
+        return {"every": o.every, "offset": o.offset, "nsub": o.nsub, "noise": bool(o.noise), "statics": bool(o.statics),
+                "dk": o.dk, "dc": o.dc, "kcmax": o.kcmax, "dt": o.dt, "lam": lam, "lnlam": lnlam, "norm": norm}
+
+    def nuis_set(self, kn, kc):
+        """Replace the values (indices inside the ladder, |kc| <= kcmax); logL is
+        recomputed from the tables the sampler holds, without an eikonal solve."""
+        p = self.p
+        kn, kc = np.ascontiguousarray(kn, dtype=np.int32), np.ascontiguousarray(kc, dtype=np.int32)
+        if kn.shape != (self.nchains, p.nphase) or kc.shape != (self.nchains, p.nphase, p.nstat):
+            raise ValueError(f"nuis_set: kn {(self.nchains, p.nphase)} and kc {(self.nchains, p.nphase, p.nstat)}")
+        rc = self._L.mceik_mcmc_nuis_set(self._h, kn.ctypes.data_as(C.c_void_p), kc.ctypes.data_as(C.c_void_p))
+        if rc != 0:
+            raise (ValueError if rc == 1 else RuntimeError)(
+                f"mceik_mcmc_nuis_set failed ({rc}): after nuis_enable, indices inside the ladder, statics inside the box")
+
+    def nuis_stats(self, reset=False):
+        """(attempts, accepts) int64 [nphase + nphase * nstat] over the chains:
+        entry ph the noise index of phase ph, entry nphase + ph * nstat + k the
+        static of station k (a pair counts on both its stations)."""
+        n = self.p.nphase * (1 + self.p.nstat)
+        att, acc = np.zeros(n, np.int64), np.zeros(n, np.int64)
+        self._nuis_held(self._L.mceik_mcmc_nuis_stats(self._h, att.ctypes.data_as(C.c_void_p),
+                                                      acc.ctypes.data_as(C.c_void_p), int(reset)), "mceik_mcmc_nuis_stats")
+        if self._nuis_base is not None:
+            att, acc = att + self._nuis_base[0], acc + self._nuis_base[1]
+        if reset:
+            self._nuis_base = None
+        return att, acc
+
+    def nuis_last(self):
+        """The last nuisance step, per chain and sub-move: (rec int32 [nchains,
+        nsub, 4] = parameter (numbered as in `nuis_stats`), partner parameter
+        (-1: a noise move), the parameter's candidate value, accepted; logl
+        float64 [nchains, nsub, 2] = logL before the sub-move, logL' of the
+        candidate (outside its box: logL))."""
+        nsub = self.nuis_options()["nsub"]
+        rec, logl = np.zeros((self.nchains, nsub, 4), np.int32), np.zeros((self.nchains, nsub, 2))
+        self._nuis_held(self._L.mceik_mcmc_nuis_last(self._h, rec.ctypes.data_as(C.c_void_p),
+                                                     logl.ctypes.data_as(C.c_void_p)), "mceik_mcmc_nuis_last")
+        return rec, logl
+
+    def nuis_moments(self):
+        """{"n", "ksum" [nphase, 2] = sums of k, k^2, "hist" [nphase, nk], "csum"
+        [nphase, nstat, 2] = sums of kc, kc^2}: exact int64 sums over the cold
+        chains' kept states since `nuis_enable`; ranks merge them by addition."""
+        p, nk = self.p, self.nuis_options()["lam"].size
+        n = C.c_longlong(0)
+        ks, hist, cs = np.zeros((p.nphase, 2), np.int64), np.zeros((p.nphase, nk), np.int64), \
+            np.zeros((p.nphase, p.nstat, 2), np.int64)
+        self._nuis_held(self._L.mceik_mcmc_nuis_moments_get(self._h, C.byref(n), ks.ctypes.data_as(C.c_void_p),
+                                                            hist.ctypes.data_as(C.c_void_p), cs.ctypes.data_as(C.c_void_p)),
+                        "mceik_mcmc_nuis_moments_get")
+        return {"n": n.value, "ksum": ks, "hist": hist, "csum": cs}
+
+    def nuis_moments_set(self, m):
+        """Load moments (`nuis_moments`' dict: a checkpoint's, or merged ones)."""
+        ks, hist, cs = (np.ascontiguousarray(m[k], dtype=np.int64) for k in ("ksum", "hist", "csum"))
+        ref = self.nuis_moments()
+        if any(a.shape != ref[k].shape for a, k in ((ks, "ksum"), (hist, "hist"), (cs, "csum"))):
+            raise ValueError("nuis_moments_set: moments of another sampler shape or ladder")
+        self._nuis_held(self._L.mceik_mcmc_nuis_moments_set(self._h, int(m["n"]), ks.ctypes.data_as(C.c_void_p),
+                                                            hist.ctypes.data_as(C.c_void_p), cs.ctypes.data_as(C.c_void_p)),
+                        "mceik_mcmc_nuis_moments_set")
+
+    def nuis_summary(self, moments=None):
+        """{"lnlam_mean", "lnlam_std" [nphase], "static_mean", "static_std"
+        [nphase, nstat] in seconds} over the cold chains' kept states, from the
+        moments (this sampler's, or merged ones) and the ladder's histogram;
+        NaN without states."""
+        m = self.nuis_moments() if moments is None else moments
+        o = self.nuis_options()
+        n, p = int(m["n"]), self.p
+        if n <= 0:
+            nan1, nan2 = np.full(p.nphase, np.nan), np.full((p.nphase, p.nstat), np.nan)
+            return {"lnlam_mean": nan1, "lnlam_std": nan1.copy(), "static_mean": nan2, "static_std": nan2.copy()}
+        w = np.asarray(m["hist"], np.float64) / n
+        mu = w @ o["lnlam"]
+        var = np.maximum(w @ (o["lnlam"] ** 2) - mu * mu, 0.0)
+        cs = np.asarray(m["csum"], np.float64) / n
+        cvar = np.maximum(cs[..., 1] - cs[..., 0] ** 2, 0.0)
+        return {"lnlam_mean": mu, "lnlam_std": np.sqrt(var), "static_mean": cs[..., 0] * o["dt"],
+                "static_std": np.sqrt(cvar) * o["dt"]}
 
     def fsm_stats(self, reset=False):
         """(FSM kernel ms from hipEvents, launches, executed iterations summed over
