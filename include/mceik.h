@@ -577,6 +577,97 @@ int mceik_mcmc_nuis_moments_set(mceik_mcmc *s, long long n, const long long *ksu
 int mceik_nuis_draw(uint32_t seed, uint32_t gchain, uint64_t step, int sub, int nnoise, int nact0, int nact1, int dk,
                     int dc, int m[5], double *logu);
 
+/* ---- probe-to-cell covariances / trade-off maps (csrc/cov.hip)
+ * Off by default; with it off nothing changes.  Every other summary is a
+ * marginal; this one streams, for 1 <= np <= 64 probe quantities, the exact
+ * cross-moments of each probe with every model entry, so that a row of the
+ * (out of reach) joint covariance can be read: how a cell, an event's depth or
+ * a station's static co-varies with the whole model.  A probe is one int32
+ * scalar of a chain, named by (kind, index):
+ *   kind 0  model entry      v[c][index]            index in [0, nphase * ncell)
+ *   kind 1  hypocentre       hyp[c][e][axis]        index = 3 e + axis (node units); needs the positions held
+ *                                                   (after the first hypo_enable, also after hypo_disable)
+ *   kind 2  station static   kc[c][ph][stat]        index = ph * nstat + stat; needs nuisance state with statics on
+ *   kind 3  noise index      kn[c][ph]              index = ph; needs nuisance state with noise on
+ * Duplicate probes are allowed.  With x_p probe p's value and v_j model entry
+ * j, over the cold chains c and the accumulated states t the sampler keeps in
+ * int64 (ncm = nphase * ncell)
+ *   n                        states per chain
+ *   A[np] = sum x_p          G[np][np] = sum x_p x_q
+ *   S[ncm] = sum v_j         Q[ncm] = sum v_j^2         C[np][ncm] = sum x_p v_j
+ * and with within = 1 also the per-chain sums A_c[nchains][np] = sum_t x_p and
+ * S_c[nchains][ncm] = sum_t v_j (rows of hot chains stay zero).  Memory: 8 (np
+ * + 2) ncm bytes pooled (17 MB at 32 768 entries and 64 probes), within = 1
+ * adds 8 nchains (ncm + np) (269 MB at 1024 chains).  Every word is an exact
+ * integer sum: the order of accumulation, pipes, shards and ranks do not
+ * matter.  A word wraps after 2^63 / (max |x| * vmax) accumulated states
+ * (chains x kept steps): more than 1e11 at the default prior.
+ *
+ * While enabled, mceik_mcmc_run adds the state after every kept step (the rule
+ * of the kept states and of the posterior, whatever max_samples is) by two
+ * kernels queued behind the step: no host synchronisation, and the chains are
+ * bit for bit those of a run without it.  With multi-step launches a launch
+ * ends right after the next kept step, as for the streaming posterior.
+ *
+ * enable returns 1 for np outside [1, 64], an unknown kind, an index out of
+ * range, a probe whose state is not held, and while the accumulators hold
+ * states of another probe list or another `within`; with the list and
+ * `within` of the held sums it resumes them.  disable stops accumulating and
+ * keeps the sums; clear drops them.  While a kind 2 or 3 probe is registered
+ * and accumulation is enabled, mceik_mcmc_nuis_clear returns 1.
+ * Every function returns 0, 1 on invalid arguments or -1 on a device failure. */
+#define MCEIK_COV_MAX_PROBES 64
+typedef struct mceik_cov_opts {
+    int np;
+    int kind[MCEIK_COV_MAX_PROBES], index[MCEIK_COV_MAX_PROBES];
+    int within;
+} mceik_cov_opts;
+typedef struct mceik_cov_partials {            /* caller-allocated host arrays */
+    int np, ncm, within;
+    int kind[MCEIK_COV_MAX_PROBES], index[MCEIK_COV_MAX_PROBES];
+    long long nchains, nkept;                  /* chains summed, states per chain */
+    long long *A, *S;                          /* [np], [ncm] */
+    /* 128-bit two's complement, lo then hi word: sums of products ... */
+    unsigned long long *G, *Q, *C;             /* [np][np][2], [ncm][2], [np][ncm][2] */
+    /* ... and, within = 1 (else zero; may be NULL), sums over chains of products of per-chain sums:
+     * PA[p][q] = sum_c A_c[c][p] A_c[c][q],  P[j] = sum_c S_c[c][j]^2,  T[p][j] = sum_c A_c[c][p] S_c[c][j] */
+    unsigned long long *PA, *P, *T;            /* [np][np][2], [ncm][2], [np][ncm][2] */
+} mceik_cov_partials;
+int mceik_mcmc_cov_enable(mceik_mcmc *s, const mceik_cov_opts *o);
+int mceik_mcmc_cov_disable(mceik_mcmc *s);
+int mceik_mcmc_cov_clear(mceik_mcmc *s);
+/* Adds the cold chains' current state now (enqueued on the sampler's stream). */
+int mceik_mcmc_cov_accumulate(mceik_mcmc *s);
+/* Host copies of / replacements for the accumulators (checkpoints): n, A [np],
+ * G [np][np], S, Q [ncm], C [np][ncm], Ac [nchains][np], Sc [nchains][ncm]
+ * (the last two with within = 1 only).  get synchronises, any pointer may be
+ * NULL; set needs every array the sampler holds. */
+int mceik_mcmc_cov_get(mceik_mcmc *s, long long *n, long long *A, long long *G, long long *S, long long *Q,
+                       long long *C, long long *Ac, long long *Sc);
+int mceik_mcmc_cov_set(mceik_mcmc *s, long long n, const long long *A, const long long *G, const long long *S,
+                       const long long *Q, const long long *C, const long long *Ac, const long long *Sc);
+/* The accumulators as partials, and with within = 1 the chain axis reduced on
+ * the device into PA, P and T.  Fills every scalar of *out, the probe list and
+ * the arrays it points to.  Synchronises. */
+int mceik_mcmc_cov_partials(mceik_mcmc *s, mceik_cov_partials *out);
+/* Host only (no GPU call).  merge: dst += src, every word with its carry; 1
+ * unless np, the probe lists, ncm, within and nkept agree.  finish: with M =
+ * nchains, n = nkept, N = M n every numerator is an exact 128-bit integer
+ * converted to double once, then only *, / and sqrt:
+ *   cov[p][j]   = (N C - A_p S_j) / (N (N - 1)),  var_x[p] from G_pp, var_v[j] from Q_j likewise
+ *   corr[p][j]  = cov / sqrt(var_x[p] var_v[j])
+ *   covw[p][j]  = (n C - T) / (M n (n - 1)),  Wx[p] = (n G_pp - PA_pp) / (M n (n - 1)),  Wv[j] = (n Q_j - P_j) / (M n (n - 1))
+ *   corrw[p][j] = covw / sqrt(Wx[p] Wv[j])
+ * (pooled over all chains and states; within-chain: about each chain's own
+ * mean, meaningful while R-hat is not yet 1).  pmean[p] = A_p / N; pcov, pcorr,
+ * pcovw, pcorrw [np][np] come the same way from G and PA.  NaN: the pooled
+ * quantities when N < 2 (pmean when N = 0), the within-chain ones when within
+ * = 0, n < 2 or M < 1, a correlation whose variance numerator is 0.  cov, corr,
+ * covw, corrw: [np][ncm]; any output may be NULL. */
+int mceik_cov_merge(mceik_cov_partials *dst, const mceik_cov_partials *src);
+int mceik_cov_finish(const mceik_cov_partials *p, double *cov, double *corr, double *covw, double *corrw, double *pmean,
+                     double *pcov, double *pcorr, double *pcovw, double *pcorrw);
+
 /* ---- multi-rank runs (one process per GPU; csrc/comm.hip) ---------------
  * The sampler's only collective is the checkpoint gather (SURVEY s.8e) over
  * RCCL (xGMI on one node).  Bootstrap as RCCL's: rank 0 calls

@@ -126,6 +126,24 @@ class NuisOpts(C.Structure):
                 ("lam", C.c_void_p), ("lnlam", C.c_void_p), ("norm", C.c_void_p)]
 
 
+COV_MAX_PROBES = 64
+
+
+class CovOpts(C.Structure):
+    """mceik_cov_opts (include/mceik.h)."""
+    _fields_ = [("np", C.c_int), ("kind", C.c_int * COV_MAX_PROBES), ("index", C.c_int * COV_MAX_PROBES),
+                ("within", C.c_int)]
+
+
+class CovPartials(C.Structure):
+    """mceik_cov_partials (include/mceik.h): caller-allocated host arrays."""
+    _fields_ = [("np", C.c_int), ("ncm", C.c_int), ("within", C.c_int),
+                ("kind", C.c_int * COV_MAX_PROBES), ("index", C.c_int * COV_MAX_PROBES),
+                ("nchains", C.c_longlong), ("nkept", C.c_longlong),
+                ("A", C.c_void_p), ("S", C.c_void_p), ("G", C.c_void_p), ("Q", C.c_void_p), ("C", C.c_void_p),
+                ("PA", C.c_void_p), ("P", C.c_void_p), ("T", C.c_void_p)]
+
+
 # every extern "C" symbol include/*.h declares
 EXPORTS = ("eikonal3d_serial_driver", "eikonal3d_serial_driver_sp", "eikonal3d_batch_solve", "eikonal3d_initialize", "eikonal3d_solve",
            "eikonal3d_finalize", "locate3d_gridsearch__double64", "locate3d_gridsearch__float64",
@@ -154,6 +172,8 @@ EXPORTS = ("eikonal3d_serial_driver", "eikonal3d_serial_driver_sp", "eikonal3d_b
            "mceik_mcmc_nuis_enable", "mceik_mcmc_nuis_disable", "mceik_mcmc_nuis_clear", "mceik_mcmc_nuis_get",
            "mceik_mcmc_nuis_set", "mceik_mcmc_nuis_stats", "mceik_mcmc_nuis_last", "mceik_mcmc_nuis_moments_get",
            "mceik_mcmc_nuis_moments_set", "mceik_nuis_draw",
+           "mceik_mcmc_cov_enable", "mceik_mcmc_cov_disable", "mceik_mcmc_cov_clear", "mceik_mcmc_cov_accumulate",
+           "mceik_mcmc_cov_get", "mceik_mcmc_cov_set", "mceik_mcmc_cov_partials", "mceik_cov_merge", "mceik_cov_finish",
            "mceik_parms_defaults", "mceik_parms_set", "mceik_parms_read", "mceik_parms_args", "mceik_parms_write",
            "mceik_comm_available", "mceik_comm_unique_id", "mceik_comm_init", "mceik_comm_finalize", "mceik_mcmc_gather",
            "os_path_exists", "os_path_isdir", "os_path_isfile", "os_makedirs", "os_mkdir")
@@ -337,5 +357,20 @@ def lib():
     L.mceik_mcmc_nuis_moments_set.argtypes = [C.c_void_p, C.c_longlong] + [C.c_void_p] * 3
     L.mceik_nuis_draw.restype = C.c_int
     L.mceik_nuis_draw.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64] + [C.c_int] * 6 + [C.c_void_p, C.POINTER(C.c_double)]
+    L.mceik_mcmc_cov_enable.restype = C.c_int
+    L.mceik_mcmc_cov_enable.argtypes = [C.c_void_p, C.POINTER(CovOpts)]
+    for name in ("mceik_mcmc_cov_disable", "mceik_mcmc_cov_clear", "mceik_mcmc_cov_accumulate"):
+        getattr(L, name).restype = C.c_int
+        getattr(L, name).argtypes = [C.c_void_p]
+    L.mceik_mcmc_cov_get.restype = C.c_int
+    L.mceik_mcmc_cov_get.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)] + [C.c_void_p] * 7
+    L.mceik_mcmc_cov_set.restype = C.c_int
+    L.mceik_mcmc_cov_set.argtypes = [C.c_void_p, C.c_longlong] + [C.c_void_p] * 7
+    L.mceik_mcmc_cov_partials.restype = C.c_int
+    L.mceik_mcmc_cov_partials.argtypes = [C.c_void_p, C.POINTER(CovPartials)]
+    L.mceik_cov_merge.restype = C.c_int
+    L.mceik_cov_merge.argtypes = [C.POINTER(CovPartials), C.POINTER(CovPartials)]
+    L.mceik_cov_finish.restype = C.c_int
+    L.mceik_cov_finish.argtypes = [C.POINTER(CovPartials)] + [C.c_void_p] * 9
     _lib = L
     return L

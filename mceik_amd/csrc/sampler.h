@@ -9,6 +9,7 @@
 
 #include "../../include/mceik.h"
 #include "block.h"
+#include "cov.h"
 #include "fsm_common.h"
 #include "hypo.h"
 #include "nuis.h"
@@ -19,7 +20,7 @@
 #define MCEIK_MAX_PIPES 4
 #define MCEIK_ITERS_N (6 + MCEIK_TRAFFIC_N)   // d_iters: iterations, 4 visit statistics, solves, traffic
 
-// A pipe: a part of the chains stepped on a stream of its own.  D, B, P, H, N, fb
+// A pipe: a part of the chains stepped on a stream of its own.  D, B, P, H, N, C, fb
 // and fb_hyp are views of the sampler's restricted to the pipe's chains;
 // pipes_refresh alone writes them.
 struct Pipe {
@@ -28,6 +29,7 @@ struct Pipe {
     PriorDev P;
     HypoDev H;
     NuisDev N;
+    CovDev C;                          // (all null while the sampler holds no covariance accumulators)
     mceik_fsm_batch fb;
     mceik_fsm_batch fb_hyp;            // a hypocentre step's batch (every model of the pipe's chains)
     void *ws;                          // the pipe's workspace: a part of the sampler's ws, ws itself, or its own
@@ -127,6 +129,12 @@ struct mceik_mcmc {
     float *ttab_cur1;                  // one model: [nchains][nstat][nev] current tables while N.kn is set
     long long nuis_n;                  // states in the moments (cold chains x kept steps)
     std::vector<int> h_ostat, h_omask, h_ophase;   // [nobs] the observations' station, mask and phase (host copies)
+    // Probe-to-cell covariances (cov.hip); off by default.  cov is
+    // null until an enable and again after a clear; cov_on: kept steps add to it
+    // (a disable keeps the sums).  While on, a multi-step launch ends right
+    // after the next kept step, as it does for the posterior.
+    McmcCov *cov;
+    bool cov_on;
     hipStream_t stream;
     void *ws;
     size_t ws_bytes;
@@ -158,6 +166,6 @@ int mcmc_forward_all(mceik_mcmc *s);
 int check_forward_ierr(mceik_mcmc *s, const char *who);
 int temper_cold(const mceik_mcmc *s);
 int temper_round(mceik_mcmc *s, int parity);
-// Recomputes every pipe's D, B, P, H, N and fb from the sampler's (and a multi-step
-// sampler's device copy of D): call after any change to s->D, s->B, s->P or s->fb.
+// Recomputes every pipe's D, B, P, H, N, C and fb from the sampler's (and a multi-step
+// sampler's device copy of D): call after any change to s->D, s->B, s->P, s->cov or s->fb.
 int pipes_refresh(mceik_mcmc *s);

@@ -4,7 +4,7 @@
 //
 // Host orchestration only.  The numerics live in fsm_kernel.hip,
 // fsm16_kernel.hip, mcmc_kernels.hip, temper.hip, block.hip, prior.hip,
-// hypo.hip, nuis.hip and posterior.hip.
+// hypo.hip, nuis.hip, posterior.hip and cov.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -190,6 +190,17 @@ static NuisDev dev_view(const NuisDev &N, const McmcDev &D, int off)
     return V;
 }
 
+// The same view of the covariance accumulators' per-chain arrays (the pooled sums are the sampler's).
+static CovDev dev_view(const CovDev &C, int off)
+{
+    CovDev V = C;
+    const size_t o = (size_t)off;
+    if (V.X) V.X += o * C.np;
+    if (V.Ac) V.Ac += o * C.np;
+    if (V.Sc) V.Sc += o * C.ncm;
+    return V;
+}
+
 // Chains [off, off + n) of the hypocentre step's batch: nphase models per
 // chain.  It runs in the workspace of the pipe's step batch sb, so it keeps at
 // most that batch's resident waves (the workspace grows with the waves only).
@@ -239,6 +250,7 @@ int pipes_refresh(mceik_mcmc *s)
         p.fb = batch_view(s->fb, lo, n, (size_t)s->D.ncm);
         p.H = dev_view(s->H, s->D, lo);
         p.N = dev_view(s->N, s->D, lo);
+        p.C = s->cov ? dev_view(mcmc_cov_dev(s->cov), lo) : CovDev();
         if (s->H.hyp) p.fb_hyp = hyp_batch_view(s->fb_hyp, p.fb, lo, n, (size_t)s->D.ncm, s->D.nphase);
     }
     // the longest-first order covers the whole batch: one pipe's (mcmc_forward)
@@ -682,6 +694,15 @@ static hipError_t post_add(mceik_mcmc *s, const McmcDev &V, int off, hipStream_t
     return mcmc_post_accumulate(s->post, W, off, st);
 }
 
+// The covariance accumulators see the cold chains only, as the posterior does
+// (post_add): the first chains of pipe p's view (chains [off, ...) of the sampler).
+static hipError_t cov_add(mceik_mcmc *s, const Pipe &p, int off, hipStream_t st)
+{
+    const int G = temper_cold(s);
+    if (off >= G) return hipSuccess;
+    return mcmc_cov_accumulate(p.C, p.D, p.H, p.N, std::min(p.D.nchains, G - off), st);
+}
+
 // A swap round belongs to step gs and runs before its proposal.
 static bool swap_step(const mceik_mcmc *s, long long gs)
 {
@@ -740,9 +761,9 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
         // FSM launch (the kernel accepts, keeps and proposes the rest)
         for (int done = 0; done < nsteps;) {
             int n = std::min(nsteps - done, MCEIK_MC_CHUNK);
-            // posterior on: the launch ends right after the next kept step, when
-            // every chain's current state is its state after that step
-            if (s->post) n = (int)std::min<long long>(n, next_kept_step(s) - s->step + 1);
+            // posterior or covariances on: the launch ends right after the next kept
+            // step, when every chain's current state is its state after that step
+            if (s->post || s->cov_on) n = (int)std::min<long long>(n, next_kept_step(s) - s->step + 1);
             // tempering: this step's swap round first; the launch ends before the next one
             if (swap_step(s, s->step) && temper_round(s, (int)((s->step / s->swap_every) & 1))) return -1;
             if (s->ntemps > 1 && s->swap_every > 0)
@@ -759,6 +780,10 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
                 HIPCHK(post_add(s, s->D, 0, s->stream));
                 mcmc_post_counted(s->post);
             }
+            if (s->cov_on && kept_step(s, s->step - 1)) {
+                HIPCHK(cov_add(s, s->pipe[0], 0, s->stream));      // one pipe: it views every chain
+                mcmc_cov_counted(s->cov);
+            }
             if (s->report) clock_report(s, "steps");
             done += n;
         }
@@ -770,6 +795,7 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
         uint64_t step = (uint64_t)s->step;
         int slot = -1;
         const bool post = s->post && kept_step(s, s->step);
+        const bool cov = s->cov_on && kept_step(s, s->step);
         const bool hstep = hypo_step(s, s->step), hmom = s->hypo_on && kept_step(s, s->step);
         const bool nstep = !hstep && nuis_is_step(s, s->step), nmom = s->nuis_on && s->N.kn && kept_step(s, s->step);
         if (s->max_samples && s->step >= s->nburn && (s->step - s->nburn) % s->keepk == 0) {
@@ -808,8 +834,10 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
                 HIPCHK(post_add(s, p.D, p.D.chain_offset - s->D.chain_offset, st));
             if (hmom) HIPCHK(hypo_add(s, p.D, p.H, p.D.chain_offset - s->D.chain_offset, st));
             if (nmom) HIPCHK(nuis_add(s, p.D, p.N, p.D.chain_offset - s->D.chain_offset, st));
+            if (cov) HIPCHK(cov_add(s, p, p.D.chain_offset - s->D.chain_offset, st));
         }
         if (post) mcmc_post_counted(s->post);
+        if (cov) mcmc_cov_counted(s->cov);
         if (hmom) s->hyp_n += temper_cold(s);
         if (nmom) s->nuis_n += temper_cold(s);
         if (s->report) clock_report(s, "step");
@@ -862,6 +890,7 @@ extern "C" int mceik_mcmc_finalize(mceik_mcmc **ps)
     for (Pipe &p : s->pipe) if (p.ws_own && p.ws) hipFree(p.ws);
     for (void *p : s->allocs) hipFree(p);
     mcmc_post_free(s->post);
+    mcmc_cov_free(s->cov);
     for (int i = 0; i < 2 * s->ev_made; i++) hipEventDestroy(s->ev[i]);
     if (s->ws) hipFree(s->ws);
     delete s;

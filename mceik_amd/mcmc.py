@@ -530,6 +530,7 @@ class Sampler:
         self._hypo_base = None          # (attempts, accepts) of a restored checkpoint, as _temper_base
         self._nuis = None               # the options while the sampler holds nuisance state (nuis_enable .. nuis_clear)
         self._nuis_base = None          # (attempts, accepts) of a restored checkpoint, as _temper_base
+        self._cov = None                # (probes [(kind, index)], within) while the sampler holds covariance sums
 
     @property
     def model_shape(self):
@@ -638,6 +639,8 @@ class Sampler:
             kn, kc = self.nuis_get()
             ck["nuis"] = {"opts": dict(self._nuis), "kn": kn, "kc": kc, "attempts": att, "accepts": acc,
                           "moments": self.nuis_moments()}
+        if self._cov is not None:        # the sums belong to the state of a run that summarises itself
+            ck["cov"] = self.cov_raw()
         return ck
 
     def restore(self, ck, recompute_logl=False):
@@ -670,6 +673,10 @@ class Sampler:
             recompute_logl = True
         elif self._nuis is not None:
             recompute_logl = True
+        ck_cov = ck.get("cov")           # a sampler without the sums ignores the entry; one with them wants its list
+        if ck_cov is not None and self._cov is not None and \
+                ([tuple(int(x) for x in pr) for pr in ck_cov["probes"]], bool(ck_cov["within"])) != self._cov:
+            raise ValueError("the checkpoint's covariance sums were accumulated with another probe list or `within`")
         v = np.ascontiguousarray(ck["v"], dtype=np.int32)
         assert v.shape == self.model_shape
         logl = None if recompute_logl else np.ascontiguousarray(ck["logl"], dtype=np.float64)
@@ -703,6 +710,8 @@ class Sampler:
             self.nuis_stats(reset=True)
             self._nuis_base = (np.asarray(nk["attempts"], np.int64).copy(), np.asarray(nk["accepts"], np.int64).copy())
             self.nuis_moments_set(nk["moments"])
+        if ck_cov is not None and self._cov is not None:
+            self._cov_set(ck_cov)
 
     # --- streaming posterior (include/mceik.h mceik_mcmc_posterior_*) ---
     def posterior_enable(self, per_chain=True, nbins=64):
@@ -1224,6 +1233,121 @@ class Sampler:
         return {"lnlam_mean": mu, "lnlam_std": np.sqrt(var), "static_mean": cs[..., 0] * o["dt"],
                 "static_std": np.sqrt(cvar) * o["dt"]}
 
+    # --- probe-to-cell covariances (include/mceik.h mceik_mcmc_cov_*) ---
+    def _cov_probe(self, pr):
+        """(kind, index) of one probe tuple."""
+        p = self.p
+        pr = tuple(pr)
+        name, args = pr[0], tuple(int(x) for x in pr[1:])
+
+        def flat(a, b, nb):              # a * nb + b with b inside its row (the library checks the rest)
+            if not 0 <= b < nb:
+                raise ValueError(f"cov_enable: probe {pr!r} out of range")
+            return a * nb + b
+        if name == "model" and len(args) == 1:
+            return 0, args[0]
+        if name == "model" and len(args) == 2:
+            return 0, flat(args[0], args[1], p.ncell)
+        if name == "hypo" and len(args) == 2:
+            return 1, flat(args[0], args[1], 3)
+        if name == "static" and len(args) == 2:
+            return 2, flat(args[0], args[1], p.nstat)
+        if name == "noise" and len(args) == 1:
+            return 3, args[0]
+        raise ValueError(f"cov_enable: a probe is ('model', entry), ('model', phase, cell), ('hypo', event, axis), "
+                         f"('static', phase, station) or ('noise', phase), not {pr!r}")
+
+    def cov_enable(self, probes, within=False):
+        """Stream the exact cross-moments of up to 64 probe scalars with every
+        model entry over the cold chains' kept states of run() (DESIGN.md
+        s.16): `cov_summary` then gives each probe's covariance and correlation
+        map.  `probes`: ("model", entry) or ("model", phase, cell), ("hypo",
+        event, axis) in node units (after a first `hypo_enable`), ("static",
+        phase, station) and ("noise", phase) (while `nuis_enable`'s values are
+        held with that part on); duplicates are allowed.  `within` also keeps
+        per-chain sums (8 bytes per chain and entry) for the within-chain
+        maps.  The chains do not change.  Enabling again with the list and
+        `within` of held sums resumes them (`cov_disable` keeps them,
+        `cov_clear` drops them); another list is refused while they hold states."""
+        lst = [self._cov_probe(pr) for pr in probes]
+        if not 1 <= len(lst) <= _lib.COV_MAX_PROBES:
+            raise ValueError("cov_enable: 1 to 64 probes")
+        o = _lib.CovOpts()
+        o.np, o.within = len(lst), int(bool(within))
+        for k, (kind, idx) in enumerate(lst):
+            o.kind[k], o.index[k] = kind, idx
+        rc = self._L.mceik_mcmc_cov_enable(self._h, C.byref(o))
+        if rc != 0:
+            raise (ValueError if rc == 1 else RuntimeError)(
+                f"mceik_mcmc_cov_enable failed ({rc}): indices in range, hypocentre / static / noise probes only while "
+                "that state is held, and no held sums of another probe list or `within`")
+        self._cov = (lst, bool(within))
+
+    def cov_disable(self):
+        """Stop accumulating; the sums stay (`cov_raw`, `cov_partials`, a later `cov_enable` of the same list)."""
+        if self._L.mceik_mcmc_cov_disable(self._h) != 0:
+            raise RuntimeError("mceik_mcmc_cov_disable failed")
+
+    def cov_clear(self):
+        """Drop the sums and the probe list."""
+        if self._L.mceik_mcmc_cov_clear(self._h) != 0:
+            raise RuntimeError("mceik_mcmc_cov_clear failed")
+        self._cov = None
+
+    def _cov_on(self):
+        if self._cov is None:
+            raise RuntimeError("the covariances are not enabled (Sampler.cov_enable)")
+        return self._cov
+
+    def cov_accumulate(self):
+        """Add the cold chains' current state to the sums now (enqueued)."""
+        self._cov_on()
+        rc = self._L.mceik_mcmc_cov_accumulate(self._h)
+        if rc != 0:
+            raise RuntimeError(f"mceik_mcmc_cov_accumulate failed ({rc})")
+
+    def _cov_arrays(self):
+        lst, within = self._cov_on()
+        n, ncm, nch = len(lst), self.p.nphase * self.p.ncell, self.nchains
+        shapes = {"A": (n,), "G": (n, n), "S": (ncm,), "Q": (ncm,), "C": (n, ncm)}
+        if within:
+            shapes.update({"Ac": (nch, n), "Sc": (nch, ncm)})
+        return shapes
+
+    def cov_raw(self):
+        """The accumulators as host arrays: {"n": states per chain, "probes":
+        [(kind, index)], "within", int64 "A" [np], "G" [np, np], "S", "Q" [ncm],
+        "C" [np, ncm] and with `within` "Ac" [nchains, np], "Sc" [nchains, ncm]}."""
+        lst, within = self._cov_on()
+        out = {k: np.empty(sh, np.int64) for k, sh in self._cov_arrays().items()}
+        n = C.c_longlong(0)
+        ptr = [out[k].ctypes.data_as(C.c_void_p) if k in out else None for k in ("A", "G", "S", "Q", "C", "Ac", "Sc")]
+        rc = self._L.mceik_mcmc_cov_get(self._h, C.byref(n), *ptr)
+        if rc != 0:
+            raise RuntimeError(f"mceik_mcmc_cov_get failed ({rc})")
+        out.update({"n": n.value, "probes": list(lst), "within": within})
+        return out
+
+    def _cov_set(self, raw):
+        arr = {k: np.ascontiguousarray(raw[k], dtype=np.int64) for k in self._cov_arrays()}
+        assert all(arr[k].shape == sh for k, sh in self._cov_arrays().items())
+        ptr = [arr[k].ctypes.data_as(C.c_void_p) if k in arr else None for k in ("A", "G", "S", "Q", "C", "Ac", "Sc")]
+        rc = self._L.mceik_mcmc_cov_set(self._h, int(raw["n"]), *ptr)
+        if rc != 0:
+            raise RuntimeError(f"mceik_mcmc_cov_set failed ({rc})")
+
+    def cov_partials(self):
+        """The sums as exact partials (`CovPartials`), the chain axis of the
+        per-chain sums reduced on the GPU: what ranks exchange and merge."""
+        lst, within = self._cov_on()
+        out = CovPartials(lst, self.p.nphase * self.p.ncell, within, shape=self.model_shape[1:])
+        st = out._struct()
+        rc = self._L.mceik_mcmc_cov_partials(self._h, C.byref(st))
+        if rc != 0:
+            raise RuntimeError(f"mceik_mcmc_cov_partials failed ({rc})")
+        out.nchains, out.nkept = int(st.nchains), int(st.nkept)
+        return out
+
     def fsm_stats(self, reset=False):
         """(FSM kernel ms from hipEvents, launches, executed iterations summed over
         solves, (brick visits, column segments updated, segments changed, wave macro
@@ -1375,6 +1499,99 @@ def posterior_summary(smp: Sampler, group=None, dst=0):
         for other in every[1:]:
             parts.merge(other)
     return PosteriorSummary(parts)
+
+
+class CovPartials:
+    """Host arrays of mceik_cov_partials (include/mceik.h) for the probe list
+    `probes` [(kind, index)]: A [np] and S [ncm] int64; G [np, np, 2], Q [ncm,
+    2], C [np, ncm, 2] and, within-chain, PA, P, T of the same shapes: uint64
+    lo, hi words of 128-bit two's complement integers, over `nchains` chains
+    of `nkept` states each.  Exact integers: partials of shards or ranks merge
+    by addition, in any order.  Plain attributes, so it travels as a host
+    object (pickle)."""
+
+    def __init__(self, probes, ncm, within, nchains=0, nkept=0, shape=None):
+        self.probes = [(int(k), int(i)) for k, i in probes]
+        self.np, self.ncm, self.within = len(self.probes), int(ncm), bool(within)
+        self.nchains, self.nkept = int(nchains), int(nkept)
+        self.shape = tuple(shape) if shape is not None else (self.ncm,)
+        n = self.np
+        self.A, self.S = np.zeros(n, np.int64), np.zeros(self.ncm, np.int64)
+        self.G, self.Q, self.C = (np.zeros(sh + (2,), np.uint64) for sh in ((n, n), (self.ncm,), (n, self.ncm)))
+        self.PA, self.P, self.T = (np.zeros(sh + (2,), np.uint64) for sh in ((n, n), (self.ncm,), (n, self.ncm)))
+
+    def _struct(self):
+        st = _lib.CovPartials()
+        st.np, st.ncm, st.within = self.np, self.ncm, int(self.within)
+        for k, (kind, idx) in enumerate(self.probes[:_lib.COV_MAX_PROBES]):
+            st.kind[k], st.index[k] = kind, idx
+        st.nchains, st.nkept = self.nchains, self.nkept
+        for name in ("A", "S", "G", "Q", "C", "PA", "P", "T"):
+            setattr(st, name, getattr(self, name).ctypes.data)
+        return st
+
+    def merge(self, other):
+        """self += other (mceik_cov_merge); both must hold the same probes,
+        entries, mode and states per chain."""
+        a, b = self._struct(), other._struct()
+        rc = _lib.lib().mceik_cov_merge(C.byref(a), C.byref(b))
+        if rc != 0:
+            raise ValueError("covariance partials do not match (probes, ncm, within, nkept)")
+        self.nchains = int(a.nchains)
+        return self
+
+    def finish(self):
+        """dict of float64 arrays (mceik_cov_finish): cov, corr, cov_within,
+        corr_within [np, ncm]; probe_mean [np]; probe_cov, probe_corr,
+        probe_cov_within, probe_corr_within [np, np]."""
+        n, ncm = self.np, self.ncm
+        out = {k: np.empty((n, ncm)) for k in ("cov", "corr", "cov_within", "corr_within")}
+        out["probe_mean"] = np.empty(n)
+        out.update({k: np.empty((n, n)) for k in ("probe_cov", "probe_corr", "probe_cov_within", "probe_corr_within")})
+        st = self._struct()
+        rc = _lib.lib().mceik_cov_finish(C.byref(st), *(a.ctypes.data_as(C.c_void_p) for a in out.values()))
+        if rc != 0:
+            raise RuntimeError(f"mceik_cov_finish failed ({rc})")
+        return out
+
+
+class CovSummary:
+    """Trade-off maps from merged `CovPartials`: `cov`, `corr` (over all chains
+    and states) and `cov_within`, `corr_within` (about each chain's own mean;
+    NaN without `within`, with fewer than 2 states) of every probe with every
+    model entry, shaped [np] + one chain's model shape; `probe_mean` [np] and
+    the probe x probe `probe_cov`, `probe_corr`, `probe_cov_within`,
+    `probe_corr_within` [np, np]; `probes` [(kind, index)], `count` states per
+    chain over `nchains` chains.  A correlation with a constant quantity is NaN."""
+
+    def __init__(self, parts: CovPartials):
+        out = parts.finish()
+        sh = (parts.np,) + parts.shape
+        for k in ("cov", "corr", "cov_within", "corr_within"):
+            setattr(self, k, out[k].reshape(sh))
+        for k in ("probe_mean", "probe_cov", "probe_corr", "probe_cov_within", "probe_corr_within"):
+            setattr(self, k, out[k])
+        self.probes = list(parts.probes)
+        self.count, self.nchains, self.within = parts.nkept, parts.nchains, parts.within
+
+
+def cov_summary(smp: Sampler, group=None, dst=0):
+    """`CovSummary` of a sampler's covariance sums.  With a torch.distributed
+    `group` the ranks' exact partials are gathered as host objects and merged
+    on rank `dst`, which gets the summary of all chains; the other ranks get
+    None (as `posterior_summary`)."""
+    parts = smp.cov_partials()
+    if group is not None:
+        import torch.distributed as dist
+        rank, world = dist.get_rank(group), dist.get_world_size(group)
+        every = [None] * world if rank == dst else None
+        dist.gather_object(parts, every, dst=dst, group=group)
+        if rank != dst:
+            return None
+        parts = every[0]
+        for other in every[1:]:
+            parts.merge(other)
+    return CovSummary(parts)
 
 
 def picks_from_forward(device=0, precision=64):
