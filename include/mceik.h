@@ -697,6 +697,59 @@ int mceik_comm_finalize(mceik_comm **c);
 int mceik_mcmc_gather(mceik_mcmc *s, mceik_comm *c, int which, int nchains_total, int root, int *v_out,
                       double *logl_out);
 
+/* ---- discrete adjoint of the batched solve (csrc/adjoint.hip)
+ * For every solve (model m, station s) of a finished batch and adjoint weights
+ * ev_w[solve][e] on its event times, the exact derivative of
+ *   J = sum_e ev_w[solve][e] * t(solve, e)
+ * of the first-order solver with respect to the slowness of every inversion
+ * cell (slow_mode 1) or node (slow_mode 0), all cells at once: one adjoint
+ * solve per (model, station).  t(solve, e) is the table value the forward
+ * samples (the node ev_node, or with ev_frac the trilinear value; ev_stride as
+ * in the forward).  Arithmetic: fp64 on (double)u, IEEE + - * / and the sqrt of
+ * the boundary distance, no contraction, fixed summation orders, no atomics:
+ * the results do not depend on the launch, max_groups or the schedule
+ * (DESIGN.md s.17 gives every operation).
+ *
+ * `batch` gives the geometry, precision, slowness (slow, slow_mode, nr*,
+ * model_phase, nphase), sources (src; nsrc must be 1), events (nev, ev_node,
+ * ev_frac, ev_stride) and skip of the forward; its output pointers are not
+ * used.  u: the forward's fields (mceik_fsm_batch.u_out of the same batch,
+ * [nsolve][nz][ny][nx], fp32 or fp64 as batch->precision).  A solve of a skip
+ * row reads no field and yields zeros, niter 0, status 0.
+ *
+ * Outputs (device; any may be NULL): grad [nmodel][ncell] = the model's solves
+ * summed in station order (ncell = ncz ncy ncx, or nz ny nx in slow_mode 0),
+ * grad_solve [nsolve][ncell], lam [nsolve][nz ny nx] = the adjoint field (with
+ * unit weights the sensitivity / coverage of the picks), niter [nsolve] =
+ * iterations of eight sweeps run, the verifying one included, status [nsolve]:
+ * 0 converged, 1 the cap was hit (the outputs are those of the last
+ * iteration), 2 the source's boundary box leaves the grid (the forward's ierr
+ * 1; zeros).  maxit: cap on the iterations (0 = batch->maxit).  max_groups:
+ * cap on the resident workgroups (0 = 256); a workgroup runs its solves one
+ * after the other in its slice of the workspace, which is sized by the
+ * resident workgroups, not by the solves.  With grad and without grad_solve a
+ * workgroup takes a whole model (its stations in order).
+ *
+ * check: 0, or 1 with the reason on stderr (host only, no GPU call): NULL
+ * description, batch or u, a batch mceik_fsm_check refuses, nsrc != 1, events
+ * without ev_node or ev_w, a bad ev_stride, negative maxit or max_groups.
+ * solve enqueues on `stream` (no host synchronisation, no allocation) and
+ * returns 0, 1 (check, workspace too small) or -1 (device failure). */
+typedef struct mceik_fsm_adjoint {
+    const mceik_fsm_batch *batch;
+    const void *u;              /* device [nsolve][nz*ny*nx]                  */
+    const double *ev_w;         /* device [nsolve][nev]                       */
+    double *grad;               /* device [nmodel][ncell] or NULL             */
+    double *grad_solve;         /* device [nsolve][ncell] or NULL             */
+    double *lam;                /* device [nsolve][nz*ny*nx] or NULL          */
+    int *niter, *status;        /* device [nsolve] or NULL                    */
+    int maxit;                  /* 0: batch->maxit                            */
+    int max_groups;             /* 0: 256                                     */
+} mceik_fsm_adjoint;
+size_t mceik_fsm_adjoint_workspace_bytes(const mceik_fsm_adjoint *d);
+int mceik_fsm_adjoint_check(const mceik_fsm_adjoint *d);
+int mceik_fsm_adjoint_solve(const mceik_fsm_adjoint *d, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,13 @@ class FsmBatch(C.Structure):
                 ("skip", C.c_void_p), ("solve_count", C.c_void_p), ("ev_stride", C.c_int)]
 
 
+class FsmAdjoint(C.Structure):
+    """mceik_fsm_adjoint (include/mceik.h)."""
+    _fields_ = [("batch", C.POINTER(FsmBatch)), ("u", C.c_void_p), ("ev_w", C.c_void_p),
+                ("grad", C.c_void_p), ("grad_solve", C.c_void_p), ("lam", C.c_void_p),
+                ("niter", C.c_void_p), ("status", C.c_void_p), ("maxit", C.c_int), ("max_groups", C.c_int)]
+
+
 class RelocateBatch(C.Structure):
     """mceik_relocate_batch (include/mceik_eikonal.h)."""
     _fields_ = [("ldgrd", C.c_int), ("ngrd", C.c_int), ("nev", C.c_int), ("iwantOT", C.c_int),
@@ -152,6 +159,7 @@ EXPORTS = ("eikonal3d_serial_driver", "eikonal3d_serial_driver_sp", "eikonal3d_b
            "locate3d_initialize", "locate3d_gridsearch", "locate3d_finalize",
            "mceik_fsm_workspace_bytes", "mceik_fsm_batch_solve", "mceik_fsm_bytes_per_node_sweep", "mceik_fsm_step_z",
            "mceik_fsm_kernel_name", "mceik_fsm_lds_bytes", "mceik_fsm_check",
+           "mceik_fsm_adjoint_workspace_bytes", "mceik_fsm_adjoint_check", "mceik_fsm_adjoint_solve",
            "mceik_memcpy",
            "mceik_mcmc_init", "mceik_mcmc_run", "mceik_mcmc_set_stream", "mceik_mcmc_sync",
            "mceik_mcmc_get_state", "mceik_mcmc_get_samples", "mceik_mcmc_last", "mceik_mcmc_fsm_stats",
@@ -221,6 +229,12 @@ def lib():
     L.mceik_fsm_bytes_per_node_sweep.argtypes = [C.POINTER(FsmBatch)]
     L.mceik_fsm_batch_solve.restype = C.c_int
     L.mceik_fsm_batch_solve.argtypes = [C.POINTER(FsmBatch), C.c_void_p, C.c_size_t, C.c_void_p]
+    L.mceik_fsm_adjoint_workspace_bytes.restype = C.c_size_t
+    L.mceik_fsm_adjoint_workspace_bytes.argtypes = [C.POINTER(FsmAdjoint)]
+    L.mceik_fsm_adjoint_check.restype = C.c_int
+    L.mceik_fsm_adjoint_check.argtypes = [C.POINTER(FsmAdjoint)]
+    L.mceik_fsm_adjoint_solve.restype = C.c_int
+    L.mceik_fsm_adjoint_solve.argtypes = [C.POINTER(FsmAdjoint), C.c_void_p, C.c_size_t, C.c_void_p]
     L.mceik_memcpy.restype = C.c_int
     L.mceik_memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
     L.locate_l2_gridSearch__float64.restype = C.c_int

@@ -299,3 +299,88 @@ class BatchSolver:
         out["bytes_per_node_sweep"] = L.mceik_fsm_bytes_per_node_sweep(C.byref(b))
         out["step_z"] = L.mceik_fsm_step_z(C.byref(b))
         return out
+
+    def adjoint(self, sources, slow, u, ev_node, ev_w, ev_frac=None, want_lambda=False, want_per_solve=False,
+                skip=None, max_groups=0, maxit=None, stream=None):
+        """Discrete adjoint of `solve` (mceik_fsm_adjoint): for
+        every solve the exact derivative of sum_e ev_w[solve][e] * ttab[solve][e]
+        with respect to the slowness of every cell (mode 'cells') or node (mode
+        'field'), in fp64.  sources, slow, ev_node, ev_frac: as given to
+        `solve` (one source per station); u: its out["u"] (want_fields=True);
+        ev_w: [nsolve, nev] float64.  skip: uint8 [nphase, nstat], models
+        ordered [chain][phase]: solve (m, s) with skip[m % nphase][s] set
+        reads no field and gives zeros.  maxit caps the iterations (None: the
+        solver's maxit); max_groups the resident workgroups (0: 256).
+        Returns {"grad": [nmodel, ncell] (stations summed in order), "niter",
+        "status": [nsolve] int32 (0 converged, 1 cap hit, 2 source box outside
+        the grid), "grad_solve": [nsolve, ncell] if want_per_solve, "lam":
+        [nsolve, nz, ny, nx] if want_lambda}; ncell = nz*ny*nx in field mode."""
+        import torch
+        dev = slow.device
+        sources = sources.to(device=dev, dtype=torch.float64).contiguous()
+        nstat, nsrc = int(sources.shape[0]), int(sources.shape[1])
+        nmodel = int(slow.shape[0])
+        slow_mode = 1 if self.nref is not None else 0
+        want_dtype = torch.float64 if self.precision == 64 else torch.float32
+        if slow.dtype != (torch.float32 if slow_mode == 1 else want_dtype):
+            raise TypeError("slowness: float32 cells, or a field of the solver's precision")
+        if u is None or u.dtype != want_dtype:
+            raise TypeError(f"u must be the forward's {want_dtype} fields")
+        slow, u = slow.contiguous(), u.contiguous()
+        nsolve, n = nmodel * nstat, self.nx * self.ny * self.nz
+        if u.numel() != nsolve * n:
+            raise ValueError("u must hold one field per solve")
+        per_model = ev_node.dim() == 2
+        if per_model and int(ev_node.shape[0]) != nmodel:
+            raise ValueError("a 2-D ev_node holds one row per model")
+        nev = int(ev_node.shape[-1] if per_model else ev_node.numel())
+        ev_node = ev_node.to(device=dev, dtype=torch.int32).contiguous()
+        ev_w = torch.as_tensor(ev_w, dtype=torch.float64).to(dev).contiguous()
+        if ev_w.numel() != nsolve * nev:
+            raise ValueError("ev_w must hold nev weights per solve")
+        b = self.describe(nmodel, nstat, nsrc, slow_mode, nev)
+        b.src, b.slow, b.ev_node = sources.data_ptr(), slow.data_ptr(), ev_node.data_ptr()
+        b.ev_stride = nev if per_model else 0
+        keep = [sources, slow, u, ev_node, ev_w]
+        if ev_frac is not None:
+            ev_frac = torch.as_tensor(ev_frac, dtype=torch.float32).to(dev).contiguous()
+            if ev_frac.numel() != 3 * ev_node.numel():
+                raise ValueError("ev_frac must hold 3 fractions per event")
+            b.ev_frac = ev_frac.data_ptr()
+            keep.append(ev_frac)
+        if skip is not None:
+            skip = torch.as_tensor(skip, dtype=torch.uint8).to(dev).contiguous()
+            if skip.dim() != 2 or int(skip.shape[1]) != nstat or nmodel % int(skip.shape[0]) != 0:
+                raise ValueError("skip is [nphase, nstat] with nmodel a multiple of nphase")
+            b.skip, b.nphase = skip.data_ptr(), int(skip.shape[0])
+            keep.append(skip)
+        nr = self.nref or (1, 1, 1)
+        ncell = n if slow_mode == 0 else (-(-self.nx // nr[0])) * (-(-self.ny // nr[1])) * (-(-self.nz // nr[2]))
+        d = _lib.FsmAdjoint()
+        d.batch = C.pointer(b)
+        d.u, d.ev_w = u.data_ptr(), ev_w.data_ptr()
+        out = {"grad": torch.empty((nmodel, ncell), dtype=torch.float64, device=dev),
+               "niter": torch.empty(nsolve, dtype=torch.int32, device=dev),
+               "status": torch.empty(nsolve, dtype=torch.int32, device=dev)}
+        d.grad, d.niter, d.status = out["grad"].data_ptr(), out["niter"].data_ptr(), out["status"].data_ptr()
+        if want_per_solve:
+            out["grad_solve"] = torch.empty((nsolve, ncell), dtype=torch.float64, device=dev)
+            d.grad_solve = out["grad_solve"].data_ptr()
+        if want_lambda:
+            out["lam"] = torch.empty((nsolve, self.nz, self.ny, self.nx), dtype=torch.float64, device=dev)
+            d.lam = out["lam"].data_ptr()
+        d.maxit = int(maxit) if maxit is not None else 0
+        d.max_groups = int(max_groups)
+        L = _lib.lib()
+        if L.mceik_fsm_adjoint_check(C.byref(d)) != 0:
+            raise ValueError("mceik_fsm_adjoint_check refused the batch (reason on stderr)")
+        nbytes = L.mceik_fsm_adjoint_workspace_bytes(C.byref(d))
+        ws = getattr(self, "_adj_ws", None)
+        if ws is None or ws.numel() < nbytes or ws.device != dev:
+            ws = self._adj_ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        rc = L.mceik_fsm_adjoint_solve(C.byref(d), ws.data_ptr(), ws.numel(), C.c_void_p(st))
+        if rc != 0:
+            raise RuntimeError(f"mceik_fsm_adjoint_solve failed ({rc})")
+        out["_keep"] = keep
+        return out

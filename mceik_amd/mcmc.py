@@ -519,6 +519,7 @@ class Sampler:
         self._h = h
         self._L = L
         self.max_samples = int(max_samples)
+        self.device, self.precision = int(device), (64 if int(precision) == 64 else 32)
         self._last_full = True          # the last forward solved every model (init / restore)
         self._post = None               # (per_chain, nbins) while the streaming posterior is enabled
         self._temper = None             # (betas, swap_every) while parallel tempering is enabled
@@ -1611,6 +1612,161 @@ def picks_from_forward(device=0, precision=64):
         torch.cuda.synchronize(dev)
         return out["ttab"].cpu().numpy().reshape(p.nstat, p.nevents)
     return f
+
+
+def _pick_terms(p: Problem, ttab, var, tcorr):
+    """event_obj's arithmetic (csrc/mcmc_device.h) on the host, operation for
+    operation in fp64: per event the used picks, their weights 1 / var, xnorm,
+    the residuals tc - (te + t0) and objfn."""
+    tt = np.asarray(ttab, dtype=np.float32).astype(np.float64).reshape(max(1, p.nphase), p.nstat, p.nevents)
+    var = np.asarray(p.var if var is None else var, dtype=np.float64)
+    tcorr = np.asarray(p.tcorr if tcorr is None else tcorr, dtype=np.float64)
+    mask, phase, stat, tobs, ptr = p.obs_mask, p.obs_phase, p.obs_stat, p.tobs, p.obs_ptr
+    sqrt2i = 0.7071067811865475
+    out = []
+    for e in range(p.nevents):
+        js = [j for j in range(int(ptr[e]), int(ptr[e + 1])) if not mask[j]]
+        xnorm = 0.0
+        for j in js:
+            xnorm = xnorm + 1.0 / float(var[j])
+        t0 = 0.0
+        for j in js:
+            te = float(tt[phase[j], stat[j], e])
+            t0 = t0 + ((1.0 / float(var[j])) / xnorm) * ((float(tobs[j]) - float(tcorr[j])) - te)
+        obj, res = 0.0, []
+        for j in js:
+            te = float(tt[phase[j], stat[j], e])
+            r = (float(tobs[j]) - float(tcorr[j])) - (te + t0)
+            s = ((1.0 / float(var[j])) * sqrt2i) * r
+            obj = obj + s * s
+            res.append(r)
+        out.append((js, [1.0 / float(var[j]) for j in js], xnorm, res, obj))
+    return out
+
+
+def logl_picks(p: Problem, ttab, var=None, tcorr=None):
+    """logL = ((0 - objfn_0) - objfn_1) - ... of the tables ttab [nphase, nstat,
+    nev] ([nstat, nev] with one model): the sampler's value bit for bit (the
+    noise normalisation of DESIGN.md s.15 is the caller's).  var, tcorr [nobs]:
+    effective values (None: the catalogue's)."""
+    logl = 0.0
+    for _, _, _, _, obj in _pick_terms(p, ttab, var, tcorr):
+        logl = logl - obj
+    return logl
+
+
+def logl_pick_grad(p: Problem, ttab, var=None, tcorr=None):
+    """d logL / d te_j [nobs] (fp64, host) of `logl_picks`: the derivative of
+    the sampler's objective with respect to the table value each used pick is
+    fit against (0 for a masked pick).  The origin time t0 is the mean weighted
+    by w = 1 / var while the objective weighs residuals by w^2 / 2, so t0 does
+    not minimise it and its dependence on te stays:
+      d logL / d te_j = w_j^2 r_j - (w_j / xnorm_e) sum_{i in e} w_i^2 r_i,
+    r = tc - (te + t0), over the used picks of j's event."""
+    g = np.zeros(len(p.tobs), np.float64)
+    for js, w, xnorm, res, _ in _pick_terms(p, ttab, var, tcorr):
+        s = 0.0
+        for wi, ri in zip(w, res):
+            s = s + (wi * wi) * ri
+        for j, wj, rj in zip(js, w, res):
+            g[j] = (wj * wj) * rj - (wj / xnorm) * s
+    return g
+
+
+def logl_inputs(smp: "Sampler"):
+    """What a chain's logL depends on besides its models, as the sampler holds
+    it now: {"hyp": int32 [nchains, nev, 3] or None (the catalogue's nodes),
+    "var", "tcorr": [nchains, nobs] effective observations,
+    "norm": [nchains, nphase] the noise normalisation terms norm[ph] *
+    lnlam[kn[c][ph]], subtracted from logL in phase order}."""
+    p, nch = smp.p, smp.nchains
+    try:
+        hyp = smp.hypo_positions()
+    except RuntimeError:
+        hyp = None
+    var = np.tile(np.asarray(p.var, np.float64), (nch, 1))
+    tcorr = np.tile(np.asarray(p.tcorr, np.float64), (nch, 1))
+    norm = np.zeros((nch, max(1, p.nphase)))
+    if smp._nuis is not None:
+        kn, kc = smp.nuis_get()
+        o = smp.nuis_options()
+        ph, st = p.obs_phase, np.clip(p.obs_stat, 0, p.nstat - 1)
+        for c in range(nch):
+            if o["lam"].size:
+                var[c] = var[c] * o["lam"][kn[c][ph]]
+                norm[c] = o["norm"] * o["lnlam"][kn[c]]
+            if o["statics"]:
+                tcorr[c] = tcorr[c] + kc[c][ph, st].astype(np.float64) * o["dt"]
+    return {"hyp": hyp, "var": var, "tcorr": tcorr, "norm": norm}
+
+
+def logl_grad(smp: "Sampler", chains=None, wrt="slowness", chunk=None):
+    """Exact gradient of the log likelihood of the chosen chains' current
+    models with respect to every inversion cell: (grad float64 [nchain, nphase
+    * ncell], logl float64 [nchain]).  One forward with fields and one adjoint
+    solve per (chain, phase, station), in chunks of `chunk`
+    chains (None: sized to about 2 GiB of fields).  Honours P and P+S models,
+    mask_s, the station flags (a station without picks of a phase is skipped),
+    tt_interp, the chains' current hypocentres and their noise scale and
+    statics; logl is the sampler's own value for that state.
+
+    wrt="slowness": d logL / d s of the cell slowness s = 1 / v the forward
+    solves with; wrt="velocity": that times -1 / v^2.  This is the gradient of
+    the UNTEMPERED LIKELIHOOD only: a tempered chain's beta, the smoothness /
+    reference prior and the box are the caller's to add."""
+    import torch
+    from .eikonal import BatchSolver
+    if wrt not in ("slowness", "velocity"):
+        raise ValueError(f"wrt: 'slowness' or 'velocity', not {wrt!r}")
+    p = smp.p
+    chains = list(range(smp.nchains)) if chains is None else [int(c) for c in chains]
+    nph, nstat, nev, ncell = max(1, p.nphase), p.nstat, p.nevents, p.ncell
+    dev = torch.device("cuda", smp.device)
+    v = smp.state()[0].reshape(smp.nchains, nph, ncell)
+    inp = logl_inputs(smp)
+    bs = BatchSolver(p.nx, p.ny, p.nz, p.h, p.x0, p.y0, p.z0, p.maxit, p.tol, smp.precision, nref=p.nref,
+                     fast_sqrt=True)
+    src = torch.tensor(np.stack([np.zeros(nstat), p.sx, p.sy, p.sz], 1)[:, None, :], dtype=torch.float64)
+    if chunk is None:
+        per_chain = p.nx * p.ny * p.nz * (8 if smp.precision == 64 else 4) * nph * nstat
+        chunk = max(1, (1 << 31) // per_chain)
+    grad = np.empty((len(chains), nph * ncell), np.float64)
+    logl = np.empty(len(chains), np.float64)
+    for k0 in range(0, len(chains), int(chunk)):
+        cs = chains[k0:k0 + int(chunk)]
+        slow = torch.tensor((np.float32(1.0) / v[cs].astype(np.float32)).reshape(len(cs) * nph, ncell), device=dev)
+        if p.tt_interp:
+            node, frac = p.ev_cell
+            ev_node, ev_frac = torch.tensor(node), torch.tensor(frac)
+        elif inp["hyp"] is not None:
+            h = inp["hyp"][cs].astype(np.int64)
+            node = ((h[:, :, 2] * p.ny + h[:, :, 1]) * p.nx + h[:, :, 0]).astype(np.int32)
+            ev_node, ev_frac = torch.tensor(np.repeat(node, nph, axis=0)), None      # a row per model
+        else:
+            ev_node, ev_frac = torch.tensor(p.ev_node), None
+        fwd = bs.solve(src, slow, ev_node=ev_node, want_fields=True, ev_frac=ev_frac)
+        ttab = fwd["ttab"].cpu().numpy().reshape(len(cs), nph, nstat, nev)
+        ev_w = np.zeros((len(cs), nph, nstat, nev), np.float64)
+        for i, c in enumerate(cs):
+            dte = logl_pick_grad(p, ttab[i], inp["var"][c], inp["tcorr"][c])
+            for e in range(nev):
+                for j in range(int(p.obs_ptr[e]), int(p.obs_ptr[e + 1])):
+                    if not p.obs_mask[j]:
+                        ev_w[i, p.obs_phase[j], p.obs_stat[j], e] += dte[j]
+            ll = logl_picks(p, ttab[i], inp["var"][c], inp["tcorr"][c])
+            for term in inp["norm"][c]:
+                ll = ll - float(term)
+            logl[k0 + i] = ll
+        adj = bs.adjoint(src, slow, fwd["u"], ev_node, torch.tensor(ev_w.reshape(-1, nev)), ev_frac=ev_frac,
+                         skip=torch.tensor(p.skip))
+        if int(adj["status"].max()) != 0:
+            raise RuntimeError("logl_grad: an adjoint solve did not converge within maxit")
+        g = adj["grad"].cpu().numpy().reshape(len(cs), nph * ncell)
+        if wrt == "velocity":
+            vv = v[cs].reshape(len(cs), nph * ncell).astype(np.float64)
+            g = -(g / (vv * vv))
+        grad[k0:k0 + len(cs)] = g
+    return grad, logl
 
 
 def bench_picks(p: Problem, sigma=5e-4, device=0):
