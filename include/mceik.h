@@ -750,6 +750,95 @@ size_t mceik_fsm_adjoint_workspace_bytes(const mceik_fsm_adjoint *d);
 int mceik_fsm_adjoint_check(const mceik_fsm_adjoint *d);
 int mceik_fsm_adjoint_solve(const mceik_fsm_adjoint *d, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- gradient-informed (discrete Langevin) moves (csrc/lang.hip)
+ * Off by default; with it off nothing changes.  Every other velocity proposal
+ * draws its cell and its sign without looking at the data.  A Langevin step
+ * moves every cell of one phase model of a chain at once, each cell biased
+ * along the exact gradient of the chain's log posterior (the discrete adjoint
+ * above plus the prior's gradient): the discrete Langevin proposal of Zhang,
+ * Liu & Liu 2022 on the integer velocities.  The proposal is not symmetric, so
+ * the accept test carries a Hastings term, which costs a second gradient at
+ * the proposed state: a step is two forwards with fields and two adjoint
+ * batches of the drawn model, all on the GPU.
+ *
+ * Global step gs is a Langevin step iff gs % every == offset and it is neither
+ * a hypocentre nor a nuisance step.  It replaces that step's velocity proposal
+ * (single-cell or block); the kept-state, posterior, covariance, moments and
+ * swap-round rules apply as on any velocity step.  For chain c (global id g,
+ * beta its inverse temperature):
+ *   step draw  r = Philox4x32-10(counter {(uint32)gs, (uint32)(gs >> 32), 4, 0xFFFFFFFF}, key {g, seed})
+ *              (counter word 2: proposals 0, swaps 1, hypocentres 2, nuisance moves 3)
+ *              ph = (r0 * nphase) >> 32: every cell of model ph moves, no other;
+ *              log u = det_log((r3 + 0.5) / 2^32)
+ *   cell draw  counter {.., .., 4, i} for cell i of the model: u_i = (r0 + 0.5) / 2^32
+ *   drift      d_i = beta * g_i + gp_i (untempered: no multiply), g_i = d logL / d v_i
+ *              of the chain's current state = -(gs_i / (v_i * v_i)) with gs the
+ *              adjoint's slowness gradient under the pick weights d logL / d t
+ *              (station flags, hypocentres, noise scale, statics and tt_interp
+ *              honoured); gp_i = 0.0 with the prior off, else
+ *              -(ws * (double)(2 * sum_nb (v_i - v_nb)) + wd * (double)(2 * (v_i - vref_i)))
+ *              over the face neighbours, exact integers (no vref: the second is 0)
+ *   proposal   with c = 1 / (2 sigma sigma) and the support delta = lo..hi, lo =
+ *              max(-dmax, vlo - v_i), hi = min(dmax, vhi - v_i) ([vlo, vhi] the
+ *              phase's box, which is therefore never left):
+ *                a(delta) = (0.5 * d_i) * (double)delta - c * (double)(delta * delta)
+ *                amax = max a, w(delta) = det_exp(a(delta) - amax), Z = 0.0 + w(lo) + .. + w(hi)
+ *                delta_i = the first delta with cum + w(delta) > u_i * Z (cum from 0.0 in
+ *                support order), else hi;  log q_i(delta) = (a(delta) - amax) - det_log(Z)
+ *   lqf        = sum_i log q_i(delta_i), reduced without atomics: partial l of 256
+ *              adds cells l, l + 256, .. in order from 0.0, the total adds the
+ *              partials in order from 0.0
+ *   reverse    at v' = v + delta the same forward, pick weights and adjoint give g',
+ *              d' uses g' and the prior's gradient at v', the supports are rebuilt
+ *              about v', lqr = sum_i log q'_i(-delta_i)
+ *   accept iff log u < beta * (logL' - logL) + (lqr - lqf)
+ *              (prior on: log u folded with the exact differences of the full
+ *              integer energies of v' and v, as in the prior's accept rule)
+ * in IEEE double without contraction; det_exp is the deterministic exp next to
+ * the sampler's log (mceik_det_exp).  A chain one of whose adjoint solves
+ * returned a nonzero status, or one of whose forwards a nonzero ierr, at
+ * either state, rejects and counts as failed.  No gradient is kept between
+ * steps.  A tempering swap needs nothing new.
+ *
+ * Memory: a forward with fields stores each field twice, so a pipe walks its
+ * chains in chunks sized so that fields, workspaces and pick weights of all
+ * pipes stay under mem_bytes (0: 2 GiB); the chunk size and the number of
+ * pipes do not change a bit of the result.  Everything is allocated at
+ * enable.  While enabled every step is one launch of each kernel
+ * (mceik_mcmc_info.multi_step reports 0 until disable).
+ *
+ * enable returns 1 on NULL options, every <= 0, an offset outside [0, every),
+ * sigma <= 0, dmax < 1 or above MCEIK_LANG_DMAX_CAP, and a budget too small for
+ * one chain of a pipe.  The other functions return 1 before the first enable.
+ * Every function returns 0, 1 on invalid arguments or -1 on a device failure. */
+#define MCEIK_LANG_DMAX_CAP 32
+typedef struct mceik_lang_opts { int every, offset; double sigma; int dmax; size_t mem_bytes; } mceik_lang_opts;
+/* Turns the moves on (or replaces the options); resets the counters.  Synchronises. */
+int mceik_mcmc_lang_enable(mceik_mcmc *s, const mceik_lang_opts *o);
+/* Later steps are the sampler's other velocity proposals again. */
+int mceik_mcmc_lang_disable(mceik_mcmc *s);
+/* The options in force (every = 0 after disable; o may be NULL) and the chunk,
+ * in chains, of every pipe (chunk [npipe] or NULL). */
+int mceik_mcmc_lang_get(mceik_mcmc *s, mceik_lang_opts *o, int *chunk);
+/* Over the chains: Langevin steps tried, accepted, failed (a solve's status),
+ * and cells with delta != 0 of the accepted steps.  Any may be NULL.  Synchronises. */
+int mceik_mcmc_lang_stats(mceik_mcmc *s, long long *attempts, long long *accepts, long long *failed, long long *moved,
+                          int reset);
+/* The last Langevin step: phase [nchains], delta [nchains][ncell] of that
+ * phase's model, lqf, lqr, logL' [nchains], accept [nchains], status [nchains]
+ * (1: failed).  Any may be NULL.  Synchronises. */
+int mceik_mcmc_lang_last(mceik_mcmc *s, int *phase, int *delta, double *lqf, double *lqr, double *logl_prop,
+                         unsigned char *accept, int *status);
+/* Host only (no GPU call), the arithmetic the kernels run.  det_exp: x < -708
+ * gives 0, x > 709 inf, a NaN itself.  lang_cell: the proposal of cell `cell`
+ * of global chain gchain at global step `step` with drift d at velocity v in
+ * the box [vlo, vhi]: the drawn delta, the support's ends lo, hi and logq [hi -
+ * lo + 1] of every support value (room for 2 dmax + 1; any output may be
+ * NULL); 1 on sigma <= 0, dmax outside [1, cap], v outside the box. */
+double mceik_det_exp(double x);
+int mceik_lang_cell(uint32_t seed, uint32_t gchain, uint64_t step, int cell, double d, int v, int vlo, int vhi,
+                    double sigma, int dmax, int *delta, int *lo, int *hi, double *logq);
+
 #ifdef __cplusplus
 }
 #endif

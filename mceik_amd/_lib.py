@@ -133,6 +133,13 @@ class NuisOpts(C.Structure):
                 ("lam", C.c_void_p), ("lnlam", C.c_void_p), ("norm", C.c_void_p)]
 
 
+class LangOpts(C.Structure):
+    """mceik_lang_opts (include/mceik.h)."""
+    _fields_ = [("every", C.c_int), ("offset", C.c_int), ("sigma", C.c_double), ("dmax", C.c_int),
+                ("mem_bytes", C.c_size_t)]
+
+
+LANG_DMAX_CAP = 32
 COV_MAX_PROBES = 64
 
 
@@ -182,6 +189,8 @@ EXPORTS = ("eikonal3d_serial_driver", "eikonal3d_serial_driver_sp", "eikonal3d_b
            "mceik_mcmc_nuis_moments_set", "mceik_nuis_draw",
            "mceik_mcmc_cov_enable", "mceik_mcmc_cov_disable", "mceik_mcmc_cov_clear", "mceik_mcmc_cov_accumulate",
            "mceik_mcmc_cov_get", "mceik_mcmc_cov_set", "mceik_mcmc_cov_partials", "mceik_cov_merge", "mceik_cov_finish",
+           "mceik_mcmc_lang_enable", "mceik_mcmc_lang_disable", "mceik_mcmc_lang_get", "mceik_mcmc_lang_stats",
+           "mceik_mcmc_lang_last", "mceik_det_exp", "mceik_lang_cell",
            "mceik_parms_defaults", "mceik_parms_set", "mceik_parms_read", "mceik_parms_args", "mceik_parms_write",
            "mceik_comm_available", "mceik_comm_unique_id", "mceik_comm_init", "mceik_comm_finalize", "mceik_mcmc_gather",
            "os_path_exists", "os_path_isdir", "os_path_isfile", "os_makedirs", "os_mkdir")
@@ -319,6 +328,21 @@ def lib():
     L.mceik_mcmc_block_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.mceik_block_footprint.restype = C.c_int
     L.mceik_block_footprint.argtypes = [C.c_int] * 6 + [C.c_void_p, C.c_void_p]
+    L.mceik_mcmc_lang_enable.restype = C.c_int
+    L.mceik_mcmc_lang_enable.argtypes = [C.c_void_p, C.POINTER(LangOpts)]
+    L.mceik_mcmc_lang_disable.restype = C.c_int
+    L.mceik_mcmc_lang_disable.argtypes = [C.c_void_p]
+    L.mceik_mcmc_lang_get.restype = C.c_int
+    L.mceik_mcmc_lang_get.argtypes = [C.c_void_p, C.POINTER(LangOpts), C.c_void_p]
+    L.mceik_mcmc_lang_stats.restype = C.c_int
+    L.mceik_mcmc_lang_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_longlong)] * 4 + [C.c_int]
+    L.mceik_mcmc_lang_last.restype = C.c_int
+    L.mceik_mcmc_lang_last.argtypes = [C.c_void_p] * 8
+    L.mceik_det_exp.restype = C.c_double
+    L.mceik_det_exp.argtypes = [C.c_double]
+    L.mceik_lang_cell.restype = C.c_int
+    L.mceik_lang_cell.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int,
+                                  C.c_double, C.c_int, pi, pi, pi, C.c_void_p]
     L.mceik_mcmc_prior_enable.restype = C.c_int
     L.mceik_mcmc_prior_enable.argtypes = [C.c_void_p, C.POINTER(PriorOpts)]
     L.mceik_mcmc_prior_disable.restype = C.c_int

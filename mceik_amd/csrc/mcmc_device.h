@@ -45,6 +45,32 @@ __device__ __forceinline__ double det_log(double x)
     return de * 6.93147180369123816490e-01 + (2.0 * s * p + de * 1.90821492927058770002e-10);
 }
 
+// exp from IEEE basic operations only (host and device: the host twin is this
+// function).  k = the round-half-away integer of x log2(e), r =
+// (x - k LN2_HI) - k LN2_LO with det_log's two constants (|r| <= 0.35), the
+// Taylor polynomial of degree 13 in Horner form, times 2^k built from its bits.
+// x < -708: 0.0; x > 709: inf; a NaN is returned as it is.
+__host__ __device__ __forceinline__ double det_exp(double x)
+{
+    if (x < -708.0) return 0.0;
+    if (x > 709.0) return __builtin_inf();
+    if (!(x == x)) return x;
+    const double t = x * 1.4426950408889634;
+    const int k = (int)(t < 0.0 ? t - 0.5 : t + 0.5);
+    const double dk = (double)k;
+    const double r = (x - dk * 6.93147180369123816490e-01) - dk * 1.90821492927058770002e-10;
+    double p = 1.0 / 6227020800.0;
+    p = p * r + 1.0 / 479001600.0; p = p * r + 1.0 / 39916800.0; p = p * r + 1.0 / 3628800.0;
+    p = p * r + 1.0 / 362880.0;    p = p * r + 1.0 / 40320.0;    p = p * r + 1.0 / 5040.0;
+    p = p * r + 1.0 / 720.0;       p = p * r + 1.0 / 120.0;      p = p * r + 1.0 / 24.0;
+    p = p * r + 1.0 / 6.0;         p = p * r + 1.0 / 2.0;        p = p * r + 1.0 / 1.0;
+    p = p * r + 1.0;
+    const uint64_t b = (uint64_t)(k + 1023) << 52;
+    double s;
+    __builtin_memcpy(&s, &b, sizeof(s));
+    return p * s;
+}
+
 // A load of chain state through a vector-register address.  Inside a
 // multi-step launch the chain state changes, and a wave-uniform load may
 // otherwise become a scalar-cache load, which nothing invalidates.

@@ -12,6 +12,7 @@
 #include "cov.h"
 #include "fsm_common.h"
 #include "hypo.h"
+#include "lang.h"
 #include "nuis.h"
 #include "posterior.h"
 #include "prior.h"
@@ -20,7 +21,7 @@
 #define MCEIK_MAX_PIPES 4
 #define MCEIK_ITERS_N (6 + MCEIK_TRAFFIC_N)   // d_iters: iterations, 4 visit statistics, solves, traffic
 
-// A pipe: a part of the chains stepped on a stream of its own.  D, B, P, H, N, C, fb
+// A pipe: a part of the chains stepped on a stream of its own.  D, B, P, H, N, C, L, fb
 // and fb_hyp are views of the sampler's restricted to the pipe's chains;
 // pipes_refresh alone writes them.
 struct Pipe {
@@ -30,6 +31,7 @@ struct Pipe {
     HypoDev H;
     NuisDev N;
     CovDev C;                          // (all null while the sampler holds no covariance accumulators)
+    LangDev L;                         // (arrays null before the first lang_enable)
     mceik_fsm_batch fb;
     mceik_fsm_batch fb_hyp;            // a hypocentre step's batch (every model of the pipe's chains)
     void *ws;                          // the pipe's workspace: a part of the sampler's ws, ws itself, or its own
@@ -135,6 +137,19 @@ struct mceik_mcmc {
     // after the next kept step, as it does for the posterior.
     McmcCov *cov;
     bool cov_on;
+    // Discrete Langevin moves (lang.hip); off by default.  L's
+    // arrays are null until the first enable, which allocates everything a step
+    // uses: the per-chain arrays, and per pipe (lang_pipe) the fields, the
+    // workspaces of the forward with fields and of the adjoint, and the pick
+    // weights, sized to lang_mem.  While on, every step takes the per-step
+    // branch; global step gs is a Langevin step iff gs % lang_every ==
+    // lang_offset and it is neither a hypocentre nor a nuisance step.
+    bool lang_on;
+    int lang_every, lang_offset;
+    double lang_sigma;
+    size_t lang_mem;
+    LangDev L;
+    LangPipe lang_pipe[MCEIK_MAX_PIPES];
     hipStream_t stream;
     void *ws;
     size_t ws_bytes;
@@ -166,6 +181,11 @@ int mcmc_forward_all(mceik_mcmc *s);
 int check_forward_ierr(mceik_mcmc *s, const char *who);
 int temper_cold(const mceik_mcmc *s);
 int temper_round(mceik_mcmc *s, int parity);
-// Recomputes every pipe's D, B, P, H, N, C and fb from the sampler's (and a multi-step
+// Bytes pipe k's Langevin step needs for chunks of m chains: the fields (u), the
+// workspaces of the forward with fields (fws) and of the adjoint (aws), the
+// pick weights (evw) and the adjoint's per-solve rows (gs), each a multiple of
+// 256; returns their sum.
+size_t lang_pipe_bytes(const mceik_mcmc *s, int k, int m, size_t *u, size_t *fws, size_t *aws, size_t *evw, size_t *gs);
+// Recomputes every pipe's D, B, P, H, N, C, L and fb from the sampler's (and a multi-step
 // sampler's device copy of D): call after any change to s->D, s->B, s->P, s->cov or s->fb.
 int pipes_refresh(mceik_mcmc *s);

@@ -4,7 +4,7 @@
 //
 // Host orchestration only.  The numerics live in fsm_kernel.hip,
 // fsm16_kernel.hip, mcmc_kernels.hip, temper.hip, block.hip, prior.hip,
-// hypo.hip, nuis.hip, posterior.hip and cov.hip.
+// hypo.hip, nuis.hip, lang.hip, adjoint.hip, posterior.hip and cov.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -201,6 +201,20 @@ static CovDev dev_view(const CovDev &C, int off)
     return V;
 }
 
+// The same view of the Langevin state's per-chain arrays.
+static LangDev dev_view(const LangDev &L, const McmcDev &D, int off)
+{
+    LangDev V = L;
+    if (!L.delta) return V;
+    const size_t o = (size_t)off, os = o * D.nstat;
+    V.delta += o * D.ncell; V.vprop += o * D.ncm; V.g0 += o * D.ncell; V.g1 += o * D.ncell;
+    V.lq += 3 * o; V.nmove += o; V.status += o; V.cnt += 4 * o;
+    V.tt0 += os * D.nev;
+    V.ierr0 += os; V.ierr1 += os; V.ast0 += os; V.ast1 += os; V.niter += os;
+    V.pen += o * D.nphase;
+    return V;
+}
+
 // Chains [off, off + n) of the hypocentre step's batch: nphase models per
 // chain.  It runs in the workspace of the pipe's step batch sb, so it keeps at
 // most that batch's resident waves (the workspace grows with the waves only).
@@ -251,6 +265,7 @@ int pipes_refresh(mceik_mcmc *s)
         p.H = dev_view(s->H, s->D, lo);
         p.N = dev_view(s->N, s->D, lo);
         p.C = s->cov ? dev_view(mcmc_cov_dev(s->cov), lo) : CovDev();
+        p.L = dev_view(s->L, s->D, lo);
         if (s->H.hyp) p.fb_hyp = hyp_batch_view(s->fb_hyp, p.fb, lo, n, (size_t)s->D.ncm, s->D.nphase);
     }
     // the longest-first order covers the whole batch: one pipe's (mcmc_forward)
@@ -746,6 +761,100 @@ static hipError_t nuis_add(mceik_mcmc *s, const McmcDev &V, const NuisDev &N, in
     return nuis_moments(V, N, std::min(V.nchains, G - off), st);
 }
 
+// Global step gs is a Langevin step in place of a velocity proposal (the caller
+// has ruled out a hypocentre and a nuisance step).
+static bool lang_is_step(const mceik_mcmc *s, long long gs)
+{
+    return s->lang_on && s->lang_every > 0 && gs % s->lang_every == s->lang_offset;
+}
+
+// Chains [off, off + m) of pipe p's step batch as a Langevin step runs them:
+// the forward with fields (no skip: a skipped solve has no field) of slowness
+// `slow` into tables `ttab`, fields into u.
+static mceik_fsm_batch lang_batch(const mceik_mcmc *s, const Pipe &p, int off, int m, const float *slow, float *ttab,
+                                  void *u, int *ierr, int *niter)
+{
+    mceik_fsm_batch b = batch_view(p.fb, off, m, (size_t)s->D.ncm);
+    const size_t os = (size_t)off * b.nstat;
+    b.slow = slow + (size_t)off * s->D.ncm;
+    b.ttab = ttab + os * b.nev;
+    b.u_out = u;
+    b.skip = nullptr;
+    b.ierr = ierr + os;
+    b.niter = niter + os;
+    b.solve_order = nullptr;
+    b.solve_clock = nullptr;
+    return b;
+}
+
+static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+size_t lang_pipe_bytes(const mceik_mcmc *s, int k, int m, size_t *u, size_t *fws, size_t *aws, size_t *evw, size_t *gs)
+{
+    const Pipe &p = s->pipe[k];
+    const size_t n = (size_t)s->fb.nx * s->fb.ny * s->fb.nz, es = s->fb.precision == 64 ? 8 : 4;
+    const mceik_fsm_batch b = lang_batch(s, p, 0, m, s->D.slow_cur, s->L.tt0, (void *)s->D.slow_cur, s->d_ierr, s->d_ierr);
+    mceik_fsm_adjoint a;
+    memset(&a, 0, sizeof(a));
+    a.batch = &b;
+    a.grad = a.grad_solve = (double *)s->D.logl;      // (sizing only: one workgroup per solve)
+    *u = up256((size_t)m * b.nstat * n * es);
+    *fws = up256(mceik_fsm_workspace_bytes(&b));
+    *aws = up256(mceik_fsm_adjoint_workspace_bytes(&a));
+    *evw = up256((size_t)m * b.nstat * b.nev * sizeof(double));
+    *gs = up256((size_t)m * b.nstat * s->D.ncell * sizeof(double));
+    return *u + *fws + *aws + *evw + *gs;
+}
+
+// One Langevin step of pipe k: the step draw; at the current
+// state, chunk by chunk, the forward with fields, the pick weights and the
+// adjoint batch; the proposal; the same three at the proposed state (its
+// tables are the step's, as after any velocity proposal); the reverse log q and
+// the accept.  Everything is queued on the pipe's stream.
+static int lang_step(mceik_mcmc *s, int k, uint64_t step, int slot)
+{
+    const Pipe &p = s->pipe[k];
+    const LangPipe &lp = s->lang_pipe[k];
+    const hipStream_t st = pipe_stream(s, k);
+    const McmcDev &D = p.D;
+    const LangDev &L = p.L;
+    HIPCHK(lang_draw(D, L, step, st));
+    for (int state = 0; state < 2; state++) {
+        if (state) HIPCHK(lang_propose(D, p.B, p.P, s->prior_on, L, step, st));
+        McmcDev W = D;                  // the pick weights read the state's tables of the drawn phase
+        if (!state) W.ttab = L.tt0;
+        for (int off = 0; off < D.nchains; off += lp.chunk) {
+            const int m = std::min(lp.chunk, D.nchains - off);
+            mceik_fsm_batch b = lang_batch(s, p, off, m, state ? D.slow_prop : D.slow_cur, (float *)W.ttab, lp.u,
+                                           state ? L.ierr1 : L.ierr0, L.niter);
+            if (fsm_batch_solve_impl(&b, lp.fws, lp.fws_bytes, st, nullptr)) return -1;
+            HIPCHK(lang_weights(W, p.N, off, m, lp.ev_w, st));
+            b.skip = s->fb.skip;        // the adjoint takes the sampler's skip rows
+            mceik_fsm_adjoint a;
+            memset(&a, 0, sizeof(a));
+            a.batch = &b;
+            a.u = lp.u;
+            a.ev_w = lp.ev_w;
+            a.grad = (state ? L.g1 : L.g0) + (size_t)off * D.ncell;
+            a.grad_solve = lp.gsolve;   // a workgroup per solve; the model's rows are then summed in station order
+            a.status = (state ? L.ast1 : L.ast0) + (size_t)off * D.nstat;
+            if (mceik_fsm_adjoint_solve(&a, lp.aws, lp.aws_bytes, st)) return -1;
+        }
+    }
+    s->last_ttab = s->fb.ttab;
+    if (s->prior_on) {                  // the full integer energies of v and v' (prior.hip's kernel adds into zeroed words)
+        const size_t ps = L.pen_stride, nb = (size_t)D.nchains * D.nphase * sizeof(unsigned long long);
+        for (int q = 0; q < 4; q++) HIPCHK(hipMemsetAsync(L.pen + q * ps, 0, nb, st));
+        McmcDev V = D;
+        V.v = L.vprop;
+        HIPCHK(prior_energy(D, p.B, p.P, L.pen, L.pen + ps, st));
+        HIPCHK(prior_energy(V, p.B, p.P, L.pen + 2 * ps, L.pen + 3 * ps, st));
+    }
+    HIPCHK(lang_reverse(D, p.B, p.P, s->prior_on, L, st));
+    HIPCHK(lang_accept(D, p.N, p.P, s->prior_on, L, slot, st));
+    return 0;
+}
+
 // Steps of one call.  Returns -1 on a HIP failure; the caller joins the pipes
 // whatever happened, so the caller's stream is always ordered after every
 // kernel this call queued on the internal streams.
@@ -755,8 +864,9 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
     // sampler built for multi-step launches (one pipe) steps per launch; the
     // prior's fold sits between a step's proposal and its forward, likewise;
     // a hypocentre step has kernels and a batch of its own; nuisance state
-    // enters every logL, which the multi-step kernel's epilogue does not know
-    if (s->persist && !s->block_on && !s->prior_on && !s->hypo_on && !s->N.kn) {
+    // enters every logL, which the multi-step kernel's epilogue does not know;
+    // a Langevin step is a pipeline of launches of its own
+    if (s->persist && !s->block_on && !s->prior_on && !s->hypo_on && !s->N.kn && !s->lang_on) {
         // the first step's proposals here, then up to MCEIK_MC_CHUNK steps per
         // FSM launch (the kernel accepts, keeps and proposes the rest)
         for (int done = 0; done < nsteps;) {
@@ -798,6 +908,7 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
         const bool cov = s->cov_on && kept_step(s, s->step);
         const bool hstep = hypo_step(s, s->step), hmom = s->hypo_on && kept_step(s, s->step);
         const bool nstep = !hstep && nuis_is_step(s, s->step), nmom = s->nuis_on && s->N.kn && kept_step(s, s->step);
+        const bool lstep = !hstep && !nstep && lang_is_step(s, s->step);
         if (s->max_samples && s->step >= s->nburn && (s->step - s->nburn) % s->keepk == 0) {
             slot = s->nkept % s->max_samples;
             s->nkept++;
@@ -824,6 +935,8 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
                 HIPCHK(hypo_accept(p.D, p.H, p.N, slot, st));
             } else if (nstep) {     // nsub sub-moves per chain from the tables the chain holds: no forward
                 HIPCHK(nuis_step(p.D, p.N, step, slot, st));
+            } else if (lstep) {     // every cell of one model moves along its gradient: two forwards, two adjoints
+                if (lang_step(s, k, step, slot)) return -1;
             } else {
                 HIPCHK(blk ? block_propose(p.D, p.B, step, st) : mcmc_propose(p.D, step, st));
                 if (s->prior_on) HIPCHK(prior_fold(p.D, p.B, p.P, blk, st));
@@ -888,6 +1001,7 @@ extern "C" int mceik_mcmc_finalize(mceik_mcmc **ps)
     }
     if (s->pfork) hipEventDestroy(s->pfork);
     for (Pipe &p : s->pipe) if (p.ws_own && p.ws) hipFree(p.ws);
+    for (LangPipe &lp : s->lang_pipe) if (lp.base) hipFree(lp.base);
     for (void *p : s->allocs) hipFree(p);
     mcmc_post_free(s->post);
     mcmc_cov_free(s->cov);

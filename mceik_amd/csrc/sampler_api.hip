@@ -1,7 +1,7 @@
 // sampler_api.hip -- the sampler's accessors of the C-ABI (include/mceik.h:
 // sync, state, checkpoint / restore, kept samples, info, FSM statistics) and
-// its parallel-tempering, block-proposal, prior, hypocentre and noise / statics
-// entry points.
+// its parallel-tempering, block-proposal, prior, hypocentre, noise / statics
+// and Langevin entry points.
 // The sampler itself is sampler.hip.
 #include <hip/hip_runtime.h>
 #include <float.h>
@@ -799,6 +799,172 @@ extern "C" int mceik_nuis_draw(uint32_t seed, uint32_t gchain, uint64_t step, in
     return 0;
 }
 
+// ---------------------------------------------------------------------------
+// discrete Langevin moves (include/mceik.h mceik_mcmc_lang_*)
+
+static void lang_pipes_free(mceik_mcmc *s)
+{
+    for (LangPipe &lp : s->lang_pipe) {
+        if (lp.base) hipFree(lp.base);
+        memset(&lp, 0, sizeof(lp));
+    }
+}
+
+extern "C" int mceik_mcmc_lang_enable(mceik_mcmc *s, const mceik_lang_opts *o)
+{
+    if (!s || !o) return 1;
+    if (o->every <= 0 || o->offset < 0 || o->offset >= o->every || !(o->sigma > 0.0 && o->sigma <= DBL_MAX) ||
+        o->dmax < 1 || o->dmax > MCEIK_LANG_DMAX)
+        return 1;
+    const double c = 1.0 / (2.0 * o->sigma * o->sigma);
+    if (!(c > 0.0 && c <= DBL_MAX)) return 1;
+    const McmcDev &D = s->D;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    // the chunk of every pipe: the most chains whose fields, workspaces and pick weights fit its share of the budget
+    const size_t mem = o->mem_bytes ? o->mem_bytes : (size_t)1 << 31, share = mem / s->npipe;
+    int chunk[MCEIK_MAX_PIPES] = {0};
+    size_t need[MCEIK_MAX_PIPES][6];
+    for (int k = 0; k < s->npipe; k++) {
+        int m = s->pipe[k].D.nchains;
+        for (; m >= 1; m--) {
+            size_t *q = need[k];
+            q[5] = lang_pipe_bytes(s, k, m, &q[0], &q[1], &q[2], &q[3], &q[4]);
+            if (q[5] <= share) break;
+        }
+        if (m < 1) {
+            fprintf(stderr, "mceik_mcmc_lang_enable: mem_bytes = %zu holds no chain of pipe %d (one needs %zu B)\n", mem,
+                    k, need[k][5]);
+            return 1;
+        }
+        chunk[k] = m;
+    }
+    LangDev &L = s->L;
+    const size_t nch = D.nchains, ns = nch * D.nstat;
+    if (!L.delta) {                    // every array or none: a failed enable leaves the sampler as it was
+        LangDev A;
+        memset(&A, 0, sizeof(A));
+        if (dalloc(s, &A.delta, nch * D.ncell) || dalloc(s, &A.vprop, nch * D.ncm) || dalloc(s, &A.g0, nch * D.ncell) ||
+            dalloc(s, &A.g1, nch * D.ncell) || dalloc(s, &A.lq, 3 * nch) || dalloc(s, &A.nmove, nch) ||
+            dalloc(s, &A.status, nch) || dalloc(s, &A.tt0, ns * D.nev) || dalloc(s, &A.ierr0, ns) ||
+            dalloc(s, &A.ierr1, ns) || dalloc(s, &A.ast0, ns) || dalloc(s, &A.ast1, ns) || dalloc(s, &A.niter, ns) ||
+            dalloc(s, &A.pen, 4 * nch * D.nphase) || dalloc(s, &A.cnt, 4 * nch))
+            return -1;
+        A.pen_stride = nch * D.nphase;
+        A.skip = s->fb.skip;
+        L = A;
+    }
+    lang_pipes_free(s);
+    for (int k = 0; k < s->npipe; k++) {
+        LangPipe &lp = s->lang_pipe[k];
+        const size_t *q = need[k];
+        if (hipMalloc(&lp.base, q[5]) != hipSuccess) {
+            (void)hipGetLastError();
+            lp.base = nullptr;
+            lang_pipes_free(s);
+            s->lang_on = false;
+            fprintf(stderr, "mceik_mcmc_lang_enable: cannot allocate %zu B for pipe %d\n", q[5], k);
+            return -1;
+        }
+        char *b = (char *)lp.base;
+        lp.u = b; lp.fws = b + q[0]; lp.aws = b + q[0] + q[1]; lp.ev_w = (double *)(b + q[0] + q[1] + q[2]);
+        lp.gsolve = (double *)(b + q[0] + q[1] + q[2] + q[3]);
+        lp.fws_bytes = q[1]; lp.aws_bytes = q[2];
+        lp.chunk = chunk[k];
+    }
+    HIPCHK(hipMemset(L.cnt, 0, 4 * nch * 8));
+    L.c = c;
+    L.dmax = o->dmax;
+    s->lang_every = o->every;
+    s->lang_offset = o->offset;
+    s->lang_sigma = o->sigma;
+    s->lang_mem = mem;
+    s->lang_on = true;
+    return pipes_refresh(s);
+}
+
+extern "C" int mceik_mcmc_lang_disable(mceik_mcmc *s)
+{
+    if (!s) return 1;
+    s->lang_on = false;                // host state only: queued steps keep the kernels they were queued with
+    return 0;
+}
+
+extern "C" int mceik_mcmc_lang_get(mceik_mcmc *s, mceik_lang_opts *o, int *chunk)
+{
+    if (!s || !s->L.delta) return 1;
+    if (o) {
+        o->every = s->lang_on ? s->lang_every : 0;
+        o->offset = s->lang_offset;
+        o->sigma = s->lang_sigma;
+        o->dmax = s->L.dmax;
+        o->mem_bytes = s->lang_mem;
+    }
+    for (int k = 0; k < s->npipe && chunk; k++) chunk[k] = s->lang_pipe[k].chunk;
+    return 0;
+}
+
+extern "C" int mceik_mcmc_lang_stats(mceik_mcmc *s, long long *attempts, long long *accepts, long long *failed,
+                                     long long *moved, int reset)
+{
+    if (!s || !s->L.delta) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    const size_t nch = s->D.nchains;
+    std::vector<unsigned long long> cnt(4 * nch);
+    HIPCHK(hipMemcpy(cnt.data(), s->L.cnt, cnt.size() * 8, hipMemcpyDeviceToHost));
+    long long t[4] = {0, 0, 0, 0};
+    for (size_t c = 0; c < nch; c++)
+        for (int q = 0; q < 4; q++) t[q] += (long long)cnt[4 * c + q];
+    if (attempts) *attempts = t[0];
+    if (accepts) *accepts = t[1];
+    if (failed) *failed = t[2];
+    if (moved) *moved = t[3];
+    if (reset) HIPCHK(hipMemset(s->L.cnt, 0, cnt.size() * 8));
+    return 0;
+}
+
+extern "C" int mceik_mcmc_lang_last(mceik_mcmc *s, int *phase, int *delta, double *lqf, double *lqr, double *logl_prop,
+                                    unsigned char *accept, int *status)
+{
+    if (!s || !s->L.delta) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    const size_t nch = s->D.nchains;
+    if (phase) HIPCHK(hipMemcpy(phase, s->D.prop_phase, nch * sizeof(int), hipMemcpyDeviceToHost));
+    if (delta) HIPCHK(hipMemcpy(delta, s->L.delta, nch * s->D.ncell * sizeof(int), hipMemcpyDeviceToHost));
+    if (lqf || lqr || logl_prop) {
+        std::vector<double> lq(3 * nch);
+        HIPCHK(hipMemcpy(lq.data(), s->L.lq, lq.size() * 8, hipMemcpyDeviceToHost));
+        for (size_t c = 0; c < nch; c++) {
+            if (lqf) lqf[c] = lq[3 * c];
+            if (lqr) lqr[c] = lq[3 * c + 1];
+            if (logl_prop) logl_prop[c] = lq[3 * c + 2];
+        }
+    }
+    if (accept) HIPCHK(hipMemcpy(accept, s->D.accept, nch, hipMemcpyDeviceToHost));
+    if (status) HIPCHK(hipMemcpy(status, s->L.status, nch * sizeof(int), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" double mceik_det_exp(double x) { return mcmcd::det_exp(x); }
+
+extern "C" int mceik_lang_cell(uint32_t seed, uint32_t gchain, uint64_t step, int cell, double d, int v, int vlo, int vhi,
+                               double sigma, int dmax, int *delta, int *lo, int *hi, double *logq)
+{
+    if (cell < 0 || !(sigma > 0.0 && sigma <= DBL_MAX) || dmax < 1 || dmax > MCEIK_LANG_DMAX || v < vlo || v > vhi)
+        return 1;
+    const double c = 1.0 / (2.0 * sigma * sigma);
+    uint32_t r[4];
+    const double u = lang_uniform(seed, gchain, step, (uint32_t)cell, r);
+    const LangCell S = lang_cell(d, v, vlo, vhi, c, dmax);
+    if (delta) *delta = lang_pick(S, u);
+    if (lo) *lo = S.lo;
+    if (hi) *hi = S.hi;
+    for (int k = S.lo; k <= S.hi && logq; k++) logq[k - S.lo] = lang_logq(S, k);
+    return 0;
+}
+
 int mcmc_post_ctx(mceik_mcmc *s, McmcPostCtx *out)
 {
     if (!s || !out) return 1;
@@ -983,8 +1149,8 @@ extern "C" int mceik_mcmc_get_info(mceik_mcmc *s, mceik_mcmc_info *info)
     DeviceScope dg(s->device);
     memset(info, 0, sizeof(*info));
     info->npipe = s->npipe;
-    // block proposals, the prior, hypocentre moves and nuisance state step per launch
-    info->multi_step = s->persist && !s->block_on && !s->prior_on && !s->hypo_on && !s->N.kn ? 1 : 0;
+    // block proposals, the prior, hypocentre moves, nuisance state and Langevin moves step per launch
+    info->multi_step = s->persist && !s->block_on && !s->prior_on && !s->hypo_on && !s->N.kn && !s->lang_on ? 1 : 0;
     info->nphase = s->D.nphase;
     info->masked_s = s->masked_s;
     FsmLaunch L;

@@ -414,6 +414,28 @@ def hypo_draw(seed, gchain, step, e, dmax=(1, 1, 1)):
     return d, logu.value
 
 
+def det_exp(x):
+    """The sampler's deterministic exp (mceik_det_exp; host only): IEEE + - * /
+    only, bit for bit what the Langevin kernels compute."""
+    return float(_lib.lib().mceik_det_exp(float(x)))
+
+
+def lang_cell(seed, gchain, step, cell, d, v, vlo, vhi, sigma, dmax):
+    """The discrete Langevin proposal of one cell (mceik_lang_cell; host only):
+    cell `cell` of global chain `gchain` at global step `step`, drift d, velocity
+    v in the box [vlo, vhi].  Returns (delta, lo, logq float64 [hi - lo + 1]):
+    the drawn move, the support's lowest value and log q of every support value
+    lo, lo + 1, ..."""
+    delta, lo, hi = C.c_int(0), C.c_int(0), C.c_int(0)
+    logq = np.zeros(2 * _lib.LANG_DMAX_CAP + 1, np.float64)
+    rc = _lib.lib().mceik_lang_cell(int(seed), int(gchain), int(step), int(cell), float(d), int(v), int(vlo), int(vhi),
+                                    float(sigma), int(dmax), C.byref(delta), C.byref(lo), C.byref(hi),
+                                    logq.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise ValueError(f"lang_cell: cell >= 0, sigma > 0, 1 <= dmax <= {_lib.LANG_DMAX_CAP}, vlo <= v <= vhi")
+    return delta.value, lo.value, logq[:hi.value - lo.value + 1].copy()
+
+
 def nuis_ladder(nk, lam_min, lam_max):
     """(lam, lnlam) float64 [nk]: a log-uniform noise ladder from lam_min to
     lam_max for `Sampler.nuis_enable`, lnlam[k] = (k - nk // 2) * ln(lam_max) /
@@ -532,6 +554,7 @@ class Sampler:
         self._nuis = None               # the options while the sampler holds nuisance state (nuis_enable .. nuis_clear)
         self._nuis_base = None          # (attempts, accepts) of a restored checkpoint, as _temper_base
         self._cov = None                # (probes [(kind, index)], within) while the sampler holds covariance sums
+        self._lang = False              # Langevin moves were enabled at least once
 
     @property
     def model_shape(self):
@@ -883,6 +906,67 @@ class Sampler:
         if reset:
             self._block_base = None
         return att, acc
+
+    # --- discrete Langevin moves (include/mceik.h mceik_mcmc_lang_*) ---
+    def lang_enable(self, every, offset=0, sigma=8.0, dmax=16, mem_bytes=None):
+        """Turn gradient-informed moves on: global step gs with gs % every ==
+        offset (and neither a hypocentre nor a nuisance step) moves every cell
+        of one phase model of a chain at once, cell i by an integer in [-dmax,
+        dmax] drawn from q_i(delta) ~ exp(0.5 d_i delta - delta^2 / (2 sigma^2))
+        inside the box, d_i the exact gradient of the chain's log posterior
+        (DESIGN.md s.18), with the Hastings term of the reverse move in the
+        accept test.  A step costs two forwards with fields and two adjoint
+        batches; `mem_bytes` (None: 2 GiB) bounds the fields and workspaces it
+        holds, the chains run in chunks that fit.  Every step is then one
+        launch (`info()["multi_step"]` is False until `lang_disable`).  Resets
+        the counters."""
+        o = _lib.LangOpts(int(every), int(offset), float(sigma), int(dmax), 0 if mem_bytes is None else int(mem_bytes))
+        rc = self._L.mceik_mcmc_lang_enable(self._h, C.byref(o))
+        if rc != 0:
+            raise (ValueError if rc == 1 else RuntimeError)(
+                f"mceik_mcmc_lang_enable failed ({rc}): every > 0, 0 <= offset < every, sigma > 0, 1 <= dmax <= "
+                f"{_lib.LANG_DMAX_CAP}, mem_bytes large enough for one chain")
+        self._lang = True
+
+    def lang_disable(self):
+        if self._L.mceik_mcmc_lang_disable(self._h) != 0:
+            raise RuntimeError("mceik_mcmc_lang_disable failed")
+
+    def _lang_held(self, rc, what):
+        if rc != 0:
+            raise RuntimeError(f"{what} failed ({rc}): Langevin moves were never enabled (Sampler.lang_enable)")
+
+    def lang_options(self):
+        """The options in force (every = 0 after `lang_disable`) and "chunk": the
+        chains per chunk of every pipe."""
+        o = _lib.LangOpts()
+        chunk = np.zeros(4, np.int32)
+        self._lang_held(self._L.mceik_mcmc_lang_get(self._h, C.byref(o), chunk.ctypes.data_as(C.c_void_p)),
+                        "mceik_mcmc_lang_get")
+        return {"every": o.every, "offset": o.offset, "sigma": o.sigma, "dmax": o.dmax, "mem_bytes": o.mem_bytes,
+                "chunk": [int(x) for x in chunk[:self.info()["npipe"]]]}
+
+    def lang_stats(self, reset=False):
+        """{"attempts", "accepts", "failed", "moved"} over the chains: Langevin
+        steps tried, accepted, failed (a solve of the step did not converge),
+        and cells that changed in the accepted steps."""
+        t = [C.c_longlong(0) for _ in range(4)]
+        self._lang_held(self._L.mceik_mcmc_lang_stats(self._h, *[C.byref(x) for x in t], int(reset)),
+                        "mceik_mcmc_lang_stats")
+        return dict(zip(("attempts", "accepts", "failed", "moved"), (int(x.value) for x in t)))
+
+    def lang_last(self):
+        """The last Langevin step: {"phase" int32 [nchains], "delta" int32
+        [nchains, ncell] (the move of that phase's model, accepted or not),
+        "lqf", "lqr", "logl_prop" float64 [nchains], "accept" uint8 [nchains],
+        "status" int32 [nchains] (1: failed)}."""
+        nch, nc = self.nchains, self.p.ncell
+        out = {"phase": np.zeros(nch, np.int32), "delta": np.zeros((nch, nc), np.int32), "lqf": np.zeros(nch),
+               "lqr": np.zeros(nch), "logl_prop": np.zeros(nch), "accept": np.zeros(nch, np.uint8),
+               "status": np.zeros(nch, np.int32)}
+        self._lang_held(self._L.mceik_mcmc_lang_last(self._h, *[a.ctypes.data_as(C.c_void_p) for a in out.values()]),
+                        "mceik_mcmc_lang_last")
+        return out
 
     # --- smoothness / reference-model prior (include/mceik.h mceik_mcmc_prior_*) ---
     def prior_enable(self, sigma_smooth=None, sigma_damp=None, vref=None):
