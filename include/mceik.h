@@ -668,6 +668,103 @@ int mceik_cov_merge(mceik_cov_partials *dst, const mceik_cov_partials *src);
 int mceik_cov_finish(const mceik_cov_partials *p, double *cov, double *corr, double *covw, double *corrw, double *pmean,
                      double *pcov, double *pcorr, double *pcovw, double *pcorrw);
 
+/* ---- effective sample sizes by batch means (csrc/ess.hip) --
+ * Integrated autocorrelation time, effective sample size and Monte-Carlo
+ * standard error of every model entry (and of up to 64 probe scalars, the
+ * kinds of the covariance probes above), streamed: kept states are never
+ * stored.  Off by default; with it off nothing changes.
+ *
+ * An entry j is one of the ncm = nphase * ncell cells or, after them, one of
+ * the np probes: ne = ncm + np entries.  Batch sizes are 2^l, l = 0 ..
+ * nlevels - 1 (1 <= nlevels <= 16).  Let t = 1, 2, ... count the states added
+ * to a chain.  Per chain c and entry the sampler holds
+ *   Sc[c][j]       int64   the sum of all states added so far
+ *   pend[l][c][j]  int32   l = 0 .. nlevels - 2: the first half of the open level-(l + 1) batch
+ * and pooled over the cold chains, per level and entry, the exact sums
+ *   A[l][j]  int64     sum over chains of the chain's closed level-l batch sums
+ *   Q[l][j]  128 bits  sum over chains and closed level-l batches of B^2
+ *   P[l][j]  128 bits  sum over chains of (Sc at the chain's last level-l close)^2
+ * Adding state number t (value v; k = trailing zero bits of t, kk = min(k,
+ * nlevels - 1)):  b = v; Sc += v; for l = 0 .. kk: { A[l] += b; Q[l] += b b;
+ * P[l] += b (2 Sc - b); if (l == k && l <= nlevels - 2) { pend[l] = b; stop; }
+ * if (l < kk) b += pend[l]; }.  Every update is an integer addition: the words
+ * do not depend on the order of chains, pipes, launches, shards or ranks, and
+ * partials merge by addition.  Probe entries may be negative: A and P are
+ * two's complement, Q is unsigned.
+ *
+ * Memory: (8 + 4 (nlevels - 1)) nchains ne bytes per chain plus 40 nlevels ne
+ * pooled (1024 chains x 32 768 entries: 1.2 GB at nlevels = 8, 1.7 GB at 12).
+ * A word of pend holds a batch sum of 2^(nlevels - 2) states: enable refuses
+ * (1) when x 2^(nlevels - 2) >= 2^31 for x the largest value an entry can
+ * take: max(vmax, vsmax), a grid dimension for a hypocentre probe, kcmax for
+ * a static, the ladder length for a noise index (mceik_ess_check).  Sc and A
+ * wrap after 2^63 / x states (of a chain; of all chains); while they hold, Q
+ * and P stay below 2^127.
+ *
+ * While enabled, mceik_mcmc_run adds the cold chains' state after every kept
+ * step (the rule of the kept states and of the posterior, whatever
+ * max_samples is) by one kernel queued behind the step: no host
+ * synchronisation, and the chains are bit for bit those of a run without it.
+ * With multi-step launches a launch ends right after the next kept step, as
+ * for the streaming posterior.
+ *
+ * enable returns 1 for nlevels outside [1, 16], np outside [0, 64], an unknown
+ * kind, an index out of range, a probe whose state is not held, the bound
+ * above, and while the accumulators hold states of other options; with the
+ * options of the held sums it resumes them.  disable stops accumulating and
+ * keeps the sums; clear drops them.  While a kind 2 or 3 probe is registered
+ * and accumulation is enabled, mceik_mcmc_nuis_clear returns 1.
+ * Every function returns 0, 1 on invalid arguments or -1 on a device failure. */
+#define MCEIK_ESS_MAX_LEVELS 16
+typedef struct mceik_ess_opts {
+    int nlevels;
+    int np;                                    /* probes: 0 .. MCEIK_COV_MAX_PROBES */
+    int kind[MCEIK_COV_MAX_PROBES], index[MCEIK_COV_MAX_PROBES];
+} mceik_ess_opts;
+typedef struct mceik_ess_partials {            /* caller-allocated host arrays */
+    int ncm, np, nlevels;                      /* ne = ncm + np entries */
+    long long nchains, nkept;                  /* chains summed, states per chain */
+    long long *A;                              /* [nlevels][ne] */
+    unsigned long long *Q, *P;                 /* [nlevels][ne][2] = lo, hi words */
+} mceik_ess_partials;
+int mceik_mcmc_ess_enable(mceik_mcmc *s, const mceik_ess_opts *o);
+int mceik_mcmc_ess_disable(mceik_mcmc *s);
+int mceik_mcmc_ess_clear(mceik_mcmc *s);
+/* Adds the cold chains' current state now (enqueued on the sampler's stream). */
+int mceik_mcmc_ess_accumulate(mceik_mcmc *s);
+/* Host copies of / replacements for the accumulators (checkpoints): n states
+ * per chain, Sc [nchains][ne], pend [nlevels - 1][nchains][ne], A [nlevels][ne],
+ * Q, P [nlevels][ne][2].  get synchronises, any pointer may be NULL; set needs
+ * every array (pend only when nlevels > 1). */
+int mceik_mcmc_ess_get(mceik_mcmc *s, long long *n, long long *Sc, int *pend, long long *A, unsigned long long *Q,
+                       unsigned long long *P);
+int mceik_mcmc_ess_set(mceik_mcmc *s, long long n, const long long *Sc, const int *pend, const long long *A,
+                       const unsigned long long *Q, const unsigned long long *P);
+/* The pooled words as partials.  Fills every scalar of *out and the arrays it
+ * points to.  Synchronises. */
+int mceik_mcmc_ess_partials(mceik_mcmc *s, mceik_ess_partials *out);
+/* Host only (no GPU call).
+ * check: 0 when nlevels is in [1, 16] and xmax 2^(nlevels - 2) < 2^31, else 1.
+ * lstar: the reported level min(nlevels - 1, floor(log2(n) / 2)), a batch of
+ * about sqrt(n) states (0 for n < 1).
+ * merge: dst += src, every word with its carry; 1 unless ncm, np, nlevels and
+ * nkept agree.
+ * finish: with M = nchains, n = nkept, nb_l = n >> l the numerator N_l = nb_l
+ * Q_l - P_l is an exact 128-bit integer converted to double once, then only
+ * *, / and sqrt:
+ *   s2_l  = N_l / (M nb_l (nb_l - 1))       the within-chain variance of the level-l batch sums
+ *   tau_l = s2_l / (2^l s2_0)               the integrated autocorrelation time seen at batch size 2^l
+ *   ess   = M n / tau_L,   mcse = sqrt(s2_L / 2^L / (M n))    at L = level, or lstar when level < 0
+ * (mcse: the standard error of the mean pooled over chains and states).  NaN:
+ * tau_l where nb_l < 2; everything of an entry whose N_0 is 0 (it never moved:
+ * R-hat's rule) and when M < 1; ess and mcse where tau_L is NaN.  tau:
+ * [nlevels][ne]; ess, mcse: [ne]; any may be NULL; *level_used gets L.
+ * Returns 1 for level >= nlevels. */
+int mceik_ess_check(int nlevels, long long xmax);
+int mceik_ess_lstar(int nlevels, long long n);
+int mceik_ess_merge(mceik_ess_partials *dst, const mceik_ess_partials *src);
+int mceik_ess_finish(const mceik_ess_partials *p, int level, double *tau, double *ess, double *mcse, int *level_used);
+
 /* ---- multi-rank runs (one process per GPU; csrc/comm.hip) ---------------
  * The sampler's only collective is the checkpoint gather (SURVEY s.8e) over
  * RCCL (xGMI on one node).  Bootstrap as RCCL's: rank 0 calls

@@ -158,6 +158,22 @@ class CovPartials(C.Structure):
                 ("PA", C.c_void_p), ("P", C.c_void_p), ("T", C.c_void_p)]
 
 
+ESS_MAX_LEVELS = 16
+
+
+class EssOpts(C.Structure):
+    """mceik_ess_opts (include/mceik.h)."""
+    _fields_ = [("nlevels", C.c_int), ("np", C.c_int), ("kind", C.c_int * COV_MAX_PROBES),
+                ("index", C.c_int * COV_MAX_PROBES)]
+
+
+class EssPartials(C.Structure):
+    """mceik_ess_partials (include/mceik.h): caller-allocated host arrays."""
+    _fields_ = [("ncm", C.c_int), ("np", C.c_int), ("nlevels", C.c_int),
+                ("nchains", C.c_longlong), ("nkept", C.c_longlong),
+                ("A", C.c_void_p), ("Q", C.c_void_p), ("P", C.c_void_p)]
+
+
 # every extern "C" symbol include/*.h declares
 EXPORTS = ("eikonal3d_serial_driver", "eikonal3d_serial_driver_sp", "eikonal3d_batch_solve", "eikonal3d_initialize", "eikonal3d_solve",
            "eikonal3d_finalize", "locate3d_gridsearch__double64", "locate3d_gridsearch__float64",
@@ -189,6 +205,9 @@ EXPORTS = ("eikonal3d_serial_driver", "eikonal3d_serial_driver_sp", "eikonal3d_b
            "mceik_mcmc_nuis_moments_set", "mceik_nuis_draw",
            "mceik_mcmc_cov_enable", "mceik_mcmc_cov_disable", "mceik_mcmc_cov_clear", "mceik_mcmc_cov_accumulate",
            "mceik_mcmc_cov_get", "mceik_mcmc_cov_set", "mceik_mcmc_cov_partials", "mceik_cov_merge", "mceik_cov_finish",
+           "mceik_mcmc_ess_enable", "mceik_mcmc_ess_disable", "mceik_mcmc_ess_clear", "mceik_mcmc_ess_accumulate",
+           "mceik_mcmc_ess_get", "mceik_mcmc_ess_set", "mceik_mcmc_ess_partials", "mceik_ess_check", "mceik_ess_lstar",
+           "mceik_ess_merge", "mceik_ess_finish",
            "mceik_mcmc_lang_enable", "mceik_mcmc_lang_disable", "mceik_mcmc_lang_get", "mceik_mcmc_lang_stats",
            "mceik_mcmc_lang_last", "mceik_det_exp", "mceik_lang_cell",
            "mceik_parms_defaults", "mceik_parms_set", "mceik_parms_read", "mceik_parms_args", "mceik_parms_write",
@@ -410,5 +429,24 @@ def lib():
     L.mceik_cov_merge.argtypes = [C.POINTER(CovPartials), C.POINTER(CovPartials)]
     L.mceik_cov_finish.restype = C.c_int
     L.mceik_cov_finish.argtypes = [C.POINTER(CovPartials)] + [C.c_void_p] * 9
+    L.mceik_mcmc_ess_enable.restype = C.c_int
+    L.mceik_mcmc_ess_enable.argtypes = [C.c_void_p, C.POINTER(EssOpts)]
+    for name in ("mceik_mcmc_ess_disable", "mceik_mcmc_ess_clear", "mceik_mcmc_ess_accumulate"):
+        getattr(L, name).restype = C.c_int
+        getattr(L, name).argtypes = [C.c_void_p]
+    L.mceik_mcmc_ess_get.restype = C.c_int
+    L.mceik_mcmc_ess_get.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)] + [C.c_void_p] * 5
+    L.mceik_mcmc_ess_set.restype = C.c_int
+    L.mceik_mcmc_ess_set.argtypes = [C.c_void_p, C.c_longlong] + [C.c_void_p] * 5
+    L.mceik_mcmc_ess_partials.restype = C.c_int
+    L.mceik_mcmc_ess_partials.argtypes = [C.c_void_p, C.POINTER(EssPartials)]
+    L.mceik_ess_check.restype = C.c_int
+    L.mceik_ess_check.argtypes = [C.c_int, C.c_longlong]
+    L.mceik_ess_lstar.restype = C.c_int
+    L.mceik_ess_lstar.argtypes = [C.c_int, C.c_longlong]
+    L.mceik_ess_merge.restype = C.c_int
+    L.mceik_ess_merge.argtypes = [C.POINTER(EssPartials), C.POINTER(EssPartials)]
+    L.mceik_ess_finish.restype = C.c_int
+    L.mceik_ess_finish.argtypes = [C.POINTER(EssPartials), C.c_int] + [C.c_void_p] * 3 + [pi]
     _lib = L
     return L

@@ -29,6 +29,52 @@ struct CovDev {
     long long *Sc;                 // within: [nchains][ncm] per-chain sum of v_j, else null
 };
 
+// Where the probes' values of a view's chains live (kind -> base, row length),
+// and the probe gather itself: cov.hip's gather kernel and ess.hip's accumulate
+// kernel read a probe through the same function.
+struct CovSrc {
+    const int *v, *hyp, *kc, *kn;
+    int sv, shyp, skc, skn;
+};
+
+static inline CovSrc cov_src(const McmcDev &D, const HypoDev &H, const NuisDev &N)
+{
+    CovSrc R;
+    R.v = D.v; R.sv = D.ncm;
+    R.hyp = H.hyp; R.shyp = 3 * D.nev;
+    R.kc = N.kc; R.skc = D.nphase * D.nstat;
+    R.kn = N.kn; R.skn = D.nphase;
+    return R;
+}
+
+// The same as a table by kind, for LDS: lanes of one wave look up different
+// kinds, and a select over the kernel's arguments by kind can end up as a copy
+// of them in scratch (it did in ess.hip's kernel).
+struct CovTab {
+    const int *base[4];
+    int stride[4];
+};
+
+// Fills T (in LDS) from R; the caller synchronises the block before the first look-up.
+__device__ __forceinline__ void cov_tab_stage(CovTab &T, const CovSrc &R)
+{
+    if (threadIdx.x == 0) {
+        T.base[0] = R.v; T.base[1] = R.hyp; T.base[2] = R.kc; T.base[3] = R.kn;
+        T.stride[0] = R.sv; T.stride[1] = R.shyp; T.stride[2] = R.skc; T.stride[3] = R.skn;
+    }
+}
+
+// Probe (kind, index): where chain 0 of the view holds it, and the words from one chain to the next.
+__device__ __forceinline__ const int *cov_probe_ptr(const CovTab &T, int kind, int index, int *stride)
+{
+    *stride = T.stride[kind];
+    return T.base[kind] + index;
+}
+
+// Largest index + 1 of a probe of `kind` while the sampler holds that state, else 0
+// (cov.hip; mceik_mcmc_cov_enable and mceik_mcmc_ess_enable validate with it).
+long long mcmc_probe_limit(const mceik_mcmc *s, int kind);
+
 struct McmcCov;                    // a sampler's covariance state (cov.hip)
 
 // The step loop's side (sampler.hip mcmc_steps): the device state of p (the

@@ -25,12 +25,6 @@
 #define COV_GROUP 16               // probes per block (blockIdx.z): their accumulators stay in registers
 #define COV_RGROUP 8               // probes per block of the within-chain reduce (128-bit accumulators)
 
-// Where the probes' values of a view's chains live (kind -> base, row length).
-struct CovSrc {
-    const int *v, *hyp, *kc, *kn;
-    int sv, shyp, skc, skn;
-};
-
 // Probe gather: one block per slice of 64 chains.  X[c][p] of the slice goes to
 // LDS and to global memory (the accumulate launch reads it), A_c takes it, and
 // the slice's part of A and G goes out as one atomic per word (the slices and
@@ -38,14 +32,17 @@ struct CovSrc {
 __global__ __launch_bounds__(256) void cov_gather_kernel(CovDev V, CovSrc R, int nchains)
 {
     extern __shared__ int cov_xs[];                  // [COV_SLICE][np]
+    __shared__ CovTab tab;
     const int np = V.np, c0 = blockIdx.x * COV_SLICE;
     const int nc = nchains - c0 < COV_SLICE ? nchains - c0 : COV_SLICE;
+    cov_tab_stage(tab, R);
+    __syncthreads();
     for (int k = threadIdx.x; k < nc * np; k += 256) {
-        const int cl = k / np, p = k - cl * np, kind = V.kind[p];
+        const int cl = k / np, p = k - cl * np;
         const size_t c = (size_t)(c0 + cl);
-        const int *b = kind == 0 ? R.v : kind == 1 ? R.hyp : kind == 2 ? R.kc : R.kn;
-        const int st = kind == 0 ? R.sv : kind == 1 ? R.shyp : kind == 2 ? R.skc : R.skn;
-        const int x = b[c * st + V.index[p]];
+        int st;
+        const int *src = cov_probe_ptr(tab, V.kind[p], V.index[p], &st);
+        const int x = src[c * st];
         cov_xs[k] = x;
         V.X[c * np + p] = x;
         if (V.Ac) V.Ac[c * np + p] += x;
@@ -228,11 +225,7 @@ void mcmc_cov_free(McmcCov *p)
 hipError_t mcmc_cov_accumulate(const CovDev &V, const McmcDev &D, const HypoDev &H, const NuisDev &N, int n, hipStream_t st)
 {
     if (n <= 0) return hipSuccess;
-    CovSrc R;
-    R.v = D.v; R.sv = D.ncm;
-    R.hyp = H.hyp; R.shyp = 3 * D.nev;
-    R.kc = N.kc; R.skc = D.nphase * D.nstat;
-    R.kn = N.kn; R.skn = D.nphase;
+    const CovSrc R = cov_src(D, H, N);
     const int nslice = (n + COV_SLICE - 1) / COV_SLICE;
     hipLaunchKernelGGL(cov_gather_kernel, dim3(nslice), dim3(256), (size_t)COV_SLICE * V.np * sizeof(int), st, V, R, n);
     const dim3 grid((V.ncm + COV_TILE - 1) / COV_TILE, nslice, (V.np + COV_GROUP - 1) / COV_GROUP);
@@ -262,21 +255,25 @@ static bool cov_same(const McmcCov *p, const mceik_cov_opts *o)
     return true;
 }
 
+long long mcmc_probe_limit(const mceik_mcmc *s, int kind)
+{
+    const McmcDev &D = s->D;
+    switch (kind) {
+    case 0: return D.ncm;
+    case 1: return s->H.hyp ? 3LL * D.nev : 0;
+    case 2: return s->N.kn && s->N.statics_on ? (long long)D.nphase * D.nstat : 0;
+    case 3: return s->N.kn && s->N.noise_on ? D.nphase : 0;
+    default: return -1;
+    }
+}
+
 extern "C" int mceik_mcmc_cov_enable(mceik_mcmc *s, const mceik_cov_opts *o)
 {
     if (!s || !o || o->np < 1 || o->np > MCEIK_COV_MAX_PROBES) return 1;
     const McmcDev &D = s->D;
     for (int k = 0; k < o->np; k++) {
-        const int idx = o->index[k];
-        long long hi = 0;
-        switch (o->kind[k]) {
-        case 0: hi = D.ncm; break;
-        case 1: hi = s->H.hyp ? 3LL * D.nev : 0; break;
-        case 2: hi = s->N.kn && s->N.statics_on ? (long long)D.nphase * D.nstat : 0; break;
-        case 3: hi = s->N.kn && s->N.noise_on ? D.nphase : 0; break;
-        default: return 1;
-        }
-        if (idx < 0 || idx >= hi) return 1;         // (a probe whose state is not held has no valid index)
+        const long long hi = mcmc_probe_limit(s, o->kind[k]);
+        if (hi < 0 || o->index[k] < 0 || o->index[k] >= hi) return 1;   // (a probe whose state is not held has no valid index)
     }
     McmcCov *p = s->cov;
     if (p && !cov_same(p, o) && p->n > 0) return 1;

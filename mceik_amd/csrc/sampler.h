@@ -10,6 +10,7 @@
 #include "../../include/mceik.h"
 #include "block.h"
 #include "cov.h"
+#include "ess.h"
 #include "fsm_common.h"
 #include "hypo.h"
 #include "lang.h"
@@ -137,6 +138,12 @@ struct mceik_mcmc {
     // after the next kept step, as it does for the posterior.
     McmcCov *cov;
     bool cov_on;
+    // Effective sample sizes by batch means (ess.hip); off by
+    // default.  ess is null until an enable and again after a clear; ess_on:
+    // kept steps add to it (a disable keeps the sums).  While on, a multi-step
+    // launch ends right after the next kept step, as it does for the posterior.
+    McmcEss *ess;
+    bool ess_on;
     // Discrete Langevin moves (lang.hip); off by default.  L's
     // arrays are null until the first enable, which allocates everything a step
     // uses: the per-chain arrays, and per pipe (lang_pipe) the fields, the

@@ -4,7 +4,7 @@
 //
 // Host orchestration only.  The numerics live in fsm_kernel.hip,
 // fsm16_kernel.hip, mcmc_kernels.hip, temper.hip, block.hip, prior.hip,
-// hypo.hip, nuis.hip, lang.hip, adjoint.hip, posterior.hip and cov.hip.
+// hypo.hip, nuis.hip, lang.hip, adjoint.hip, posterior.hip, cov.hip and ess.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -718,6 +718,16 @@ static hipError_t cov_add(mceik_mcmc *s, const Pipe &p, int off, hipStream_t st)
     return mcmc_cov_accumulate(p.C, p.D, p.H, p.N, std::min(p.D.nchains, G - off), st);
 }
 
+// The batch-means accumulators see the cold chains only, as the posterior does
+// (post_add): the first chains of pipe p's view (chains [off, ...) of the
+// sampler), added as the kept state whose trailing zero bits are k.
+static hipError_t ess_add(mceik_mcmc *s, const Pipe &p, int off, int k, hipStream_t st)
+{
+    const int G = temper_cold(s);
+    if (off >= G) return hipSuccess;
+    return mcmc_ess_accumulate(s->ess, p.D, p.H, p.N, off, std::min(p.D.nchains, G - off), k, st);
+}
+
 // A swap round belongs to step gs and runs before its proposal.
 static bool swap_step(const mceik_mcmc *s, long long gs)
 {
@@ -871,9 +881,9 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
         // FSM launch (the kernel accepts, keeps and proposes the rest)
         for (int done = 0; done < nsteps;) {
             int n = std::min(nsteps - done, MCEIK_MC_CHUNK);
-            // posterior or covariances on: the launch ends right after the next kept
-            // step, when every chain's current state is its state after that step
-            if (s->post || s->cov_on) n = (int)std::min<long long>(n, next_kept_step(s) - s->step + 1);
+            // posterior, covariances or batch means on: the launch ends right after the next
+            // kept step, when every chain's current state is its state after that step
+            if (s->post || s->cov_on || s->ess_on) n = (int)std::min<long long>(n, next_kept_step(s) - s->step + 1);
             // tempering: this step's swap round first; the launch ends before the next one
             if (swap_step(s, s->step) && temper_round(s, (int)((s->step / s->swap_every) & 1))) return -1;
             if (s->ntemps > 1 && s->swap_every > 0)
@@ -894,6 +904,10 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
                 HIPCHK(cov_add(s, s->pipe[0], 0, s->stream));      // one pipe: it views every chain
                 mcmc_cov_counted(s->cov);
             }
+            if (s->ess_on && kept_step(s, s->step - 1)) {
+                HIPCHK(ess_add(s, s->pipe[0], 0, mcmc_ess_k(s->ess), s->stream));
+                mcmc_ess_counted(s->ess);
+            }
             if (s->report) clock_report(s, "steps");
             done += n;
         }
@@ -906,6 +920,8 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
         int slot = -1;
         const bool post = s->post && kept_step(s, s->step);
         const bool cov = s->cov_on && kept_step(s, s->step);
+        const bool ess = s->ess_on && kept_step(s, s->step);
+        const int ess_k = ess ? mcmc_ess_k(s->ess) : 0;      // the same for every pipe of the step
         const bool hstep = hypo_step(s, s->step), hmom = s->hypo_on && kept_step(s, s->step);
         const bool nstep = !hstep && nuis_is_step(s, s->step), nmom = s->nuis_on && s->N.kn && kept_step(s, s->step);
         const bool lstep = !hstep && !nstep && lang_is_step(s, s->step);
@@ -948,9 +964,11 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
             if (hmom) HIPCHK(hypo_add(s, p.D, p.H, p.D.chain_offset - s->D.chain_offset, st));
             if (nmom) HIPCHK(nuis_add(s, p.D, p.N, p.D.chain_offset - s->D.chain_offset, st));
             if (cov) HIPCHK(cov_add(s, p, p.D.chain_offset - s->D.chain_offset, st));
+            if (ess) HIPCHK(ess_add(s, p, p.D.chain_offset - s->D.chain_offset, ess_k, st));
         }
         if (post) mcmc_post_counted(s->post);
         if (cov) mcmc_cov_counted(s->cov);
+        if (ess) mcmc_ess_counted(s->ess);
         if (hmom) s->hyp_n += temper_cold(s);
         if (nmom) s->nuis_n += temper_cold(s);
         if (s->report) clock_report(s, "step");
@@ -1005,6 +1023,7 @@ extern "C" int mceik_mcmc_finalize(mceik_mcmc **ps)
     for (void *p : s->allocs) hipFree(p);
     mcmc_post_free(s->post);
     mcmc_cov_free(s->cov);
+    mcmc_ess_free(s->ess);
     for (int i = 0; i < 2 * s->ev_made; i++) hipEventDestroy(s->ev[i]);
     if (s->ws) hipFree(s->ws);
     delete s;

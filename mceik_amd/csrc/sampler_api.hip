@@ -680,6 +680,7 @@ extern "C" int mceik_mcmc_nuis_clear(mceik_mcmc *s)
     if (!s->N.kn) return 0;
     if (s->post && mcmc_post_count(s->post) > 0) return 1;
     if (s->cov_on && mcmc_cov_holds_nuis(s->cov)) return 1;   // a registered probe reads the values
+    if (s->ess_on && mcmc_ess_holds_nuis(s->ess)) return 1;   // likewise
     DeviceScope dg(s->device);
     HIPCHK(hipStreamSynchronize(s->stream));
     s->nuis_on = false;

@@ -555,6 +555,7 @@ class Sampler:
         self._nuis_base = None          # (attempts, accepts) of a restored checkpoint, as _temper_base
         self._cov = None                # (probes [(kind, index)], within) while the sampler holds covariance sums
         self._lang = False              # Langevin moves were enabled at least once
+        self._ess = None                # (nlevels, probes [(kind, index)]) while the sampler holds batch-means sums
 
     @property
     def model_shape(self):
@@ -665,6 +666,8 @@ class Sampler:
                           "moments": self.nuis_moments()}
         if self._cov is not None:        # the sums belong to the state of a run that summarises itself
             ck["cov"] = self.cov_raw()
+        if self._ess is not None:        # likewise: the open batches are part of a run that summarises itself
+            ck["ess"] = self.ess_raw()
         return ck
 
     def restore(self, ck, recompute_logl=False):
@@ -701,6 +704,10 @@ class Sampler:
         if ck_cov is not None and self._cov is not None and \
                 ([tuple(int(x) for x in pr) for pr in ck_cov["probes"]], bool(ck_cov["within"])) != self._cov:
             raise ValueError("the checkpoint's covariance sums were accumulated with another probe list or `within`")
+        ck_ess = ck.get("ess")           # likewise; the open batches of another hierarchy mean nothing here
+        if ck_ess is not None and self._ess is not None and \
+                (int(ck_ess["nlevels"]), [tuple(int(x) for x in pr) for pr in ck_ess["probes"]]) != self._ess:
+            raise ValueError("the checkpoint's batch-means sums were accumulated with another nlevels or probe list")
         v = np.ascontiguousarray(ck["v"], dtype=np.int32)
         assert v.shape == self.model_shape
         logl = None if recompute_logl else np.ascontiguousarray(ck["logl"], dtype=np.float64)
@@ -736,6 +743,8 @@ class Sampler:
             self.nuis_moments_set(nk["moments"])
         if ck_cov is not None and self._cov is not None:
             self._cov_set(ck_cov)
+        if ck_ess is not None and self._ess is not None:
+            self._ess_set(ck_ess)
 
     # --- streaming posterior (include/mceik.h mceik_mcmc_posterior_*) ---
     def posterior_enable(self, per_chain=True, nbins=64):
@@ -1433,6 +1442,95 @@ class Sampler:
         out.nchains, out.nkept = int(st.nchains), int(st.nkept)
         return out
 
+    # --- effective sample sizes by batch means (include/mceik.h mceik_mcmc_ess_*) ---
+    def ess_enable(self, nlevels=8, probes=()):
+        """Stream the batch-means sums of every model entry over the cold
+        chains' kept states of run(): `ess_summary` then gives
+        the integrated autocorrelation time at batch sizes 2^l, l < `nlevels`
+        <= 16, the effective sample size and the Monte-Carlo standard error of
+        the pooled mean.  `probes`: up to 64 scalars as in `cov_enable`
+        (("hypo", event, axis), ("static", phase, station), ("noise", phase),
+        ("model", ...)), further entries after the cells.  Device memory: (8 +
+        4 (nlevels - 1)) bytes per chain and entry.  The chains do not change.
+        Enabling again with the options of held sums resumes them
+        (`ess_disable` keeps them, `ess_clear` drops them); other options are
+        refused while they hold states, as is a hierarchy whose half batches
+        would not fit 32 bits (max value x 2^(nlevels - 2) >= 2^31)."""
+        lst = [self._cov_probe(pr) for pr in probes]
+        if len(lst) > _lib.COV_MAX_PROBES:
+            raise ValueError("ess_enable: at most 64 probes")
+        o = _lib.EssOpts()
+        o.nlevels, o.np = int(nlevels), len(lst)
+        for k, (kind, idx) in enumerate(lst):
+            o.kind[k], o.index[k] = kind, idx
+        rc = self._L.mceik_mcmc_ess_enable(self._h, C.byref(o))
+        if rc != 0:
+            raise (ValueError if rc == 1 else RuntimeError)(
+                f"mceik_mcmc_ess_enable failed ({rc}): nlevels in [1, 16] with max value x 2^(nlevels - 2) < 2^31, probe "
+                "indices in range and their state held, and no held sums of other options")
+        self._ess = (int(nlevels), lst)
+
+    def ess_disable(self):
+        """Stop accumulating; the sums stay (`ess_raw`, `ess_partials`, a later `ess_enable` of the same options)."""
+        if self._L.mceik_mcmc_ess_disable(self._h) != 0:
+            raise RuntimeError("mceik_mcmc_ess_disable failed")
+
+    def ess_clear(self):
+        """Drop the sums."""
+        if self._L.mceik_mcmc_ess_clear(self._h) != 0:
+            raise RuntimeError("mceik_mcmc_ess_clear failed")
+        self._ess = None
+
+    def _ess_on(self):
+        if self._ess is None:
+            raise RuntimeError("the batch-means sums are not enabled (Sampler.ess_enable)")
+        return self._ess
+
+    def ess_accumulate(self):
+        """Add the cold chains' current state to the sums now (enqueued)."""
+        self._ess_on()
+        rc = self._L.mceik_mcmc_ess_accumulate(self._h)
+        if rc != 0:
+            raise RuntimeError(f"mceik_mcmc_ess_accumulate failed ({rc})")
+
+    def _ess_arrays(self):
+        L, lst = self._ess_on()
+        ne, nch = self.p.nphase * self.p.ncell + len(lst), self.nchains
+        return {"Sc": ((nch, ne), np.int64), "pend": ((L - 1, nch, ne), np.int32), "A": ((L, ne), np.int64),
+                "Q": ((L, ne, 2), np.uint64), "P": ((L, ne, 2), np.uint64)}
+
+    def ess_raw(self):
+        """The accumulators as host arrays: {"n": states per chain, "nlevels",
+        "probes": [(kind, index)], "Sc" int64 [nchains, ne], "pend" int32
+        [nlevels - 1, nchains, ne], "A" int64 [nlevels, ne], "Q", "P" uint64
+        [nlevels, ne, 2] (lo, hi words)}; ne = the model entries, then the probes."""
+        L, lst = self._ess_on()
+        out = {k: np.zeros(sh, dt) for k, (sh, dt) in self._ess_arrays().items()}
+        n = C.c_longlong(0)
+        rc = self._L.mceik_mcmc_ess_get(self._h, C.byref(n), *(out[k].ctypes.data_as(C.c_void_p) for k in out))
+        if rc != 0:
+            raise RuntimeError(f"mceik_mcmc_ess_get failed ({rc})")
+        out.update({"n": n.value, "nlevels": L, "probes": list(lst)})
+        return out
+
+    def _ess_set(self, raw):
+        arr = {k: np.ascontiguousarray(raw[k], dtype=dt) for k, (sh, dt) in self._ess_arrays().items()}
+        assert all(arr[k].shape == sh for k, (sh, dt) in self._ess_arrays().items())
+        rc = self._L.mceik_mcmc_ess_set(self._h, int(raw["n"]), *(arr[k].ctypes.data_as(C.c_void_p) for k in arr))
+        if rc != 0:
+            raise RuntimeError(f"mceik_mcmc_ess_set failed ({rc})")
+
+    def ess_partials(self):
+        """The pooled sums as exact partials (`EssPartials`): what ranks exchange and merge."""
+        L, lst = self._ess_on()
+        out = EssPartials(self.p.nphase * self.p.ncell, L, probes=lst, shape=self.model_shape[1:])
+        st = out._struct()
+        rc = self._L.mceik_mcmc_ess_partials(self._h, C.byref(st))
+        if rc != 0:
+            raise RuntimeError(f"mceik_mcmc_ess_partials failed ({rc})")
+        out.nchains, out.nkept = int(st.nchains), int(st.nkept)
+        return out
+
     def fsm_stats(self, reset=False):
         """(FSM kernel ms from hipEvents, launches, executed iterations summed over
         solves, (brick visits, column segments updated, segments changed, wave macro
@@ -1677,6 +1775,110 @@ def cov_summary(smp: Sampler, group=None, dst=0):
         for other in every[1:]:
             parts.merge(other)
     return CovSummary(parts)
+
+
+def ess_check(nlevels, xmax):
+    """A hierarchy of `nlevels` batch sizes holds entries up to `xmax`
+    (mceik_ess_check: nlevels in [1, 16] and xmax 2^(nlevels - 2) < 2^31)."""
+    return _lib.lib().mceik_ess_check(int(nlevels), int(xmax)) == 0
+
+
+def ess_lstar(nlevels, n):
+    """The level `ess_summary` reports for n states per chain: min(nlevels - 1,
+    floor(log2(n) / 2)), a batch of about sqrt(n) states (mceik_ess_lstar)."""
+    return _lib.lib().mceik_ess_lstar(int(nlevels), int(n))
+
+
+class EssPartials:
+    """Host arrays of mceik_ess_partials (include/mceik.h) over ne = `ncm`
+    model entries + the `probes` [(kind, index)] and `nlevels` batch sizes 2^l:
+    A int64 [nlevels, ne] (sum over chains of the closed level-l batch sums), Q
+    and P uint64 [nlevels, ne, 2] (lo, hi words of 128 bits: the sum of the
+    squared batch sums; the sum over chains of the squared cumulative sum at
+    the last close), over `nchains` chains of `nkept` states each.  Exact
+    integers: partials of shards or ranks merge by addition, in any order.
+    Plain attributes, so it travels as a host object (pickle)."""
+
+    def __init__(self, ncm, nlevels, probes=(), nchains=0, nkept=0, shape=None):
+        self.probes = [(int(k), int(i)) for k, i in probes]
+        self.ncm, self.np, self.nlevels = int(ncm), len(self.probes), int(nlevels)
+        self.nchains, self.nkept = int(nchains), int(nkept)
+        self.shape = tuple(shape) if shape is not None else (self.ncm,)
+        ne = self.ncm + self.np
+        self.A = np.zeros((self.nlevels, ne), np.int64)
+        self.Q = np.zeros((self.nlevels, ne, 2), np.uint64)
+        self.P = np.zeros((self.nlevels, ne, 2), np.uint64)
+
+    def _struct(self):
+        st = _lib.EssPartials()
+        st.ncm, st.np, st.nlevels = self.ncm, self.np, self.nlevels
+        st.nchains, st.nkept = self.nchains, self.nkept
+        st.A, st.Q, st.P = self.A.ctypes.data, self.Q.ctypes.data, self.P.ctypes.data
+        return st
+
+    def merge(self, other):
+        """self += other (mceik_ess_merge); both must hold the same entries,
+        probes, levels and states per chain."""
+        a, b = self._struct(), other._struct()
+        if self.probes != other.probes or _lib.lib().mceik_ess_merge(C.byref(a), C.byref(b)) != 0:
+            raise ValueError("batch-means partials do not match (ncm, probes, nlevels, nkept)")
+        self.nchains = int(a.nchains)
+        return self
+
+    def finish(self, level=None):
+        """(tau [nlevels, ne], ess [ne], mcse [ne], level) (mceik_ess_finish);
+        level None: the one `ess_lstar` picks."""
+        ne = self.ncm + self.np
+        tau, ess, mcse = np.empty((self.nlevels, ne)), np.empty(ne), np.empty(ne)
+        st, used = self._struct(), C.c_int(0)
+        rc = _lib.lib().mceik_ess_finish(C.byref(st), -1 if level is None else int(level), tau.ctypes.data_as(C.c_void_p),
+                                         ess.ctypes.data_as(C.c_void_p), mcse.ctypes.data_as(C.c_void_p), C.byref(used))
+        if rc != 0:
+            raise ValueError(f"mceik_ess_finish failed ({rc}): level < nlevels")
+        return tau, ess, mcse, used.value
+
+
+class EssSummary:
+    """Mixing of every model entry from merged `EssPartials`: `tau_levels`
+    [nlevels, ...] the integrated autocorrelation time seen at batch size 2^l
+    (a plateau over l means the batches have outgrown the correlation; a
+    value still rising means `tau` is a lower bound), and at batch size
+    2^`level` `tau`, `ess` = nchains count / tau and `mcse`, the standard error
+    of the mean pooled over chains and states -- shaped like one chain's
+    model.  `probe_tau_levels` [nlevels, np], `probe_tau`, `probe_ess`,
+    `probe_mcse` [np]: the same for `probes` [(kind, index)].  NaN: an entry
+    that never moved, levels with fewer than two closed batches.  `count`
+    states per chain over `nchains` chains."""
+
+    def __init__(self, parts: EssPartials, level=None):
+        tau, ess, mcse, used = parts.finish(level)
+        m, sh, L = parts.ncm, parts.shape, parts.nlevels
+        self.tau_levels, self.probe_tau_levels = tau[:, :m].reshape((L,) + sh), tau[:, m:].copy()
+        self.tau, self.probe_tau = self.tau_levels[used], self.probe_tau_levels[used]
+        self.ess, self.probe_ess = ess[:m].reshape(sh), ess[m:].copy()
+        self.mcse, self.probe_mcse = mcse[:m].reshape(sh), mcse[m:].copy()
+        self.level, self.nlevels, self.probes = used, L, list(parts.probes)
+        self.count, self.nchains = parts.nkept, parts.nchains
+
+
+def ess_summary(smp: Sampler, group=None, level=None, dst=0):
+    """`EssSummary` of a sampler's batch-means sums at batch size 2^`level`
+    (None: `ess_lstar`'s choice, about sqrt(count) states).  With a
+    torch.distributed `group` the ranks' exact partials are gathered as host
+    objects and merged on rank `dst`, which gets the summary of all chains;
+    the other ranks get None (as `posterior_summary`)."""
+    parts = smp.ess_partials()
+    if group is not None:
+        import torch.distributed as dist
+        rank, world = dist.get_rank(group), dist.get_world_size(group)
+        every = [None] * world if rank == dst else None
+        dist.gather_object(parts, every, dst=dst, group=group)
+        if rank != dst:
+            return None
+        parts = every[0]
+        for other in every[1:]:
+            parts.merge(other)
+    return EssSummary(parts, level)
 
 
 def picks_from_forward(device=0, precision=64):
