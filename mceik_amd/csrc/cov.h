@@ -3,6 +3,7 @@
 // not public).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <string.h>
 
 #include "../../include/mceik.h"
 #include "hypo.h"
@@ -15,8 +16,9 @@
 // does not depend on the order in which states, chains or pipes are added.
 // Wrap bound: a word wraps after 2^63 / (max |x| * vmax) accumulated states
 // (chains x kept steps), more than 1e11 at the default prior (|x|, v <= 9000).
-// Per-chain arrays are views (sampler.hip dev_view): a pipe's CovDev points at
-// its chains' rows.  The pooled sums are the sampler's: pipes add atomically.
+// Per-chain arrays are indexed by the sampler's chain; a pipe's launch offsets
+// them (mcmc_cov_accumulate's chain_off).  The pooled sums are shared: pipes
+// add atomically.
 struct CovDev {
     int np, within, ncm;
     const int *kind, *index;       // [np] the probe list
@@ -75,15 +77,45 @@ __device__ __forceinline__ const int *cov_probe_ptr(const CovTab &T, int kind, i
 // (cov.hip; mceik_mcmc_cov_enable and mceik_mcmc_ess_enable validate with it).
 long long mcmc_probe_limit(const mceik_mcmc *s, int kind);
 
+// A registered probe list, as cov.hip and ess.hip hold theirs: the host copy
+// and the device copy [2][np] (kind, index) the kernels read.
+struct ProbeList {
+    int np;
+    int kind[MCEIK_COV_MAX_PROBES], index[MCEIK_COV_MAX_PROBES];
+    int *d;                        // kind = d, index = d + np (one word more than 2 np: np may be 0)
+};
+
+static inline bool probes_same(const ProbeList &L, int n, const int *kind, const int *index)
+{
+    return n == L.np && !memcmp(L.kind, kind, sizeof(int) * n) && !memcmp(L.index, index, sizeof(int) * n);
+}
+
+static inline bool probes_hold_nuis(const ProbeList &L)     // a static or noise-index probe is registered
+{
+    for (int k = 0; k < L.np; k++)
+        if (L.kind[k] >= 2) return true;
+    return false;
+}
+
+static inline bool probes_upload(ProbeList &L, int n, const int *kind, const int *index)     // allocates L.d
+{
+    L.np = n;
+    memcpy(L.kind, kind, sizeof(int) * n);
+    memcpy(L.index, index, sizeof(int) * n);
+    return hipMalloc((void **)&L.d, (2 * (size_t)n + 1) * sizeof(int)) == hipSuccess &&
+           (!n || (hipMemcpy(L.d, kind, n * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
+                   hipMemcpy(L.d + n, index, n * sizeof(int), hipMemcpyHostToDevice) == hipSuccess));
+}
+
 struct McmcCov;                    // a sampler's covariance state (cov.hip)
 
-// The step loop's side (sampler.hip mcmc_steps): the device state of p (the
-// sampler's view: every chain), and the first n chains of view V added on
-// stream st from the chains' state D / H / N of the same view (two launches:
+// The kept-state hook's side (sampler.hip kept_queue), in posterior.h's
+// convention: the first n chains of view D / H / N, which are chains
+// [chain_off, chain_off + n) of the sampler, added on stream st (two launches:
 // the probe gather, then the rank-n update); once every chain of a kept step
 // is queued, count the state.
-CovDev mcmc_cov_dev(const McmcCov *p);
-hipError_t mcmc_cov_accumulate(const CovDev &V, const McmcDev &D, const HypoDev &H, const NuisDev &N, int n, hipStream_t st);
+hipError_t mcmc_cov_accumulate(McmcCov *p, const McmcDev &D, const HypoDev &H, const NuisDev &N, int chain_off, int n,
+                               hipStream_t st);
 void mcmc_cov_counted(McmcCov *p);
 bool mcmc_cov_holds_nuis(const McmcCov *p);      // a static or noise-index probe is registered
 void mcmc_cov_free(McmcCov *p);

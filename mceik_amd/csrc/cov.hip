@@ -197,34 +197,31 @@ struct McmcCov {
     CovDev V;                      // every chain of the sampler
     int nchains;
     long long n;                   // states accumulated per chain
-    int kind[MCEIK_COV_MAX_PROBES], index[MCEIK_COV_MAX_PROBES];
-    int *d_probe;                  // [2][np] kind, index
+    ProbeList probes;
     unsigned long long *d_T, *d_P, *d_PA;   // within: partials scratch [np][ncm][2], [ncm][2], [np][np][2]
 };
 
-CovDev mcmc_cov_dev(const McmcCov *p) { return p->V; }
-
 void mcmc_cov_counted(McmcCov *p) { p->n++; }
 
-bool mcmc_cov_holds_nuis(const McmcCov *p)
-{
-    for (int k = 0; k < p->V.np; k++)
-        if (p->kind[k] >= 2) return true;
-    return false;
-}
+bool mcmc_cov_holds_nuis(const McmcCov *p) { return probes_hold_nuis(p->probes); }
 
 void mcmc_cov_free(McmcCov *p)
 {
     if (!p) return;
-    void *all[] = {p->d_probe, p->V.X, p->V.A, p->V.G, p->V.S, p->V.Q, p->V.C, p->V.Ac, p->V.Sc, p->d_T, p->d_P, p->d_PA};
+    void *all[] = {p->probes.d, p->V.X, p->V.A, p->V.G, p->V.S, p->V.Q, p->V.C, p->V.Ac, p->V.Sc, p->d_T, p->d_P, p->d_PA};
     for (void *q : all)
         if (q) hipFree(q);
     delete p;
 }
 
-hipError_t mcmc_cov_accumulate(const CovDev &V, const McmcDev &D, const HypoDev &H, const NuisDev &N, int n, hipStream_t st)
+hipError_t mcmc_cov_accumulate(McmcCov *p, const McmcDev &D, const HypoDev &H, const NuisDev &N, int chain_off, int n,
+                               hipStream_t st)
 {
     if (n <= 0) return hipSuccess;
+    CovDev V = p->V;                   // the chains' rows of the per-chain arrays
+    V.X += (size_t)chain_off * V.np;
+    if (V.Ac) V.Ac += (size_t)chain_off * V.np;
+    if (V.Sc) V.Sc += (size_t)chain_off * V.ncm;
     const CovSrc R = cov_src(D, H, N);
     const int nslice = (n + COV_SLICE - 1) / COV_SLICE;
     hipLaunchKernelGGL(cov_gather_kernel, dim3(nslice), dim3(256), (size_t)COV_SLICE * V.np * sizeof(int), st, V, R, n);
@@ -249,10 +246,7 @@ static long long **cov_array(McmcCov *p, int which)
 
 static bool cov_same(const McmcCov *p, const mceik_cov_opts *o)
 {
-    if (p->V.np != o->np || p->V.within != (o->within ? 1 : 0)) return false;
-    for (int k = 0; k < o->np; k++)
-        if (p->kind[k] != o->kind[k] || p->index[k] != o->index[k]) return false;
-    return true;
+    return p->V.within == (o->within ? 1 : 0) && probes_same(p->probes, o->np, o->kind, o->index);
 }
 
 long long mcmc_probe_limit(const mceik_mcmc *s, int kind)
@@ -280,7 +274,7 @@ extern "C" int mceik_mcmc_cov_enable(mceik_mcmc *s, const mceik_cov_opts *o)
     DeviceScope dg(s->device);
     if (p && cov_same(p, o)) {                      // the held sums go on
         s->cov_on = true;
-        return pipes_refresh(s);
+        return 0;
     }
     HIPCHK(hipStreamSynchronize(s->stream));
     s->cov = nullptr;
@@ -292,10 +286,8 @@ extern "C" int mceik_mcmc_cov_enable(mceik_mcmc *s, const mceik_cov_opts *o)
     p->V.within = o->within ? 1 : 0;
     p->V.ncm = D.ncm;
     p->nchains = D.nchains;
-    memcpy(p->kind, o->kind, sizeof(int) * o->np);
-    memcpy(p->index, o->index, sizeof(int) * o->np);
     const size_t np = o->np, ncm = D.ncm;
-    bool ok = hipMalloc((void **)&p->d_probe, 2 * np * sizeof(int)) == hipSuccess &&
+    bool ok = probes_upload(p->probes, o->np, o->kind, o->index) &&
               hipMalloc((void **)&p->V.X, (size_t)D.nchains * np * sizeof(int)) == hipSuccess;
     for (int a = 0; a < (p->V.within ? 7 : 5) && ok; a++) {
         ok = hipMalloc((void **)cov_array(p, a), cov_words(p, a) * 8) == hipSuccess &&
@@ -304,10 +296,7 @@ extern "C" int mceik_mcmc_cov_enable(mceik_mcmc *s, const mceik_cov_opts *o)
     if (ok && p->V.within)
         ok = hipMalloc((void **)&p->d_T, np * ncm * 16) == hipSuccess && hipMalloc((void **)&p->d_P, ncm * 16) == hipSuccess &&
              hipMalloc((void **)&p->d_PA, np * np * 16) == hipSuccess;
-    if (ok)
-        ok = hipMemcpy(p->d_probe, p->kind, np * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
-             hipMemcpy(p->d_probe + np, p->index, np * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
-             hipMemset(p->V.X, 0, (size_t)D.nchains * np * sizeof(int)) == hipSuccess;
+    if (ok) ok = hipMemset(p->V.X, 0, (size_t)D.nchains * np * sizeof(int)) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
         fprintf(stderr, "mceik_mcmc_cov_enable: out of device memory (%zu B of accumulators)\n",
@@ -315,11 +304,11 @@ extern "C" int mceik_mcmc_cov_enable(mceik_mcmc *s, const mceik_cov_opts *o)
         mcmc_cov_free(p);
         return -1;
     }
-    p->V.kind = p->d_probe;
-    p->V.index = p->d_probe + np;
+    p->V.kind = p->probes.d;
+    p->V.index = p->probes.d + np;
     s->cov = p;
     s->cov_on = true;
-    return pipes_refresh(s);
+    return 0;
 }
 
 extern "C" int mceik_mcmc_cov_disable(mceik_mcmc *s)
@@ -338,7 +327,6 @@ extern "C" int mceik_mcmc_cov_clear(mceik_mcmc *s)
     mcmc_cov_free(s->cov);
     s->cov = nullptr;
     s->cov_on = false;
-    if (pipes_refresh(s)) return -1;
     return e == hipSuccess ? 0 : -1;
 }
 
@@ -346,7 +334,7 @@ extern "C" int mceik_mcmc_cov_accumulate(mceik_mcmc *s)
 {
     if (!s || !s->cov || !s->cov_on) return 1;
     DeviceScope dg(s->device);
-    HIPCHK(mcmc_cov_accumulate(s->cov->V, s->D, s->H, s->N, temper_cold(s), s->stream));   // tempering: the cold chains
+    HIPCHK(mcmc_cov_accumulate(s->cov, s->D, s->H, s->N, 0, temper_cold(s), s->stream));   // tempering: the cold chains
     mcmc_cov_counted(s->cov);
     return 0;
 }
@@ -430,8 +418,8 @@ extern "C" int mceik_mcmc_cov_partials(mceik_mcmc *s, mceik_cov_partials *out)
     out->within = within;
     memset(out->kind, 0, sizeof(out->kind));
     memset(out->index, 0, sizeof(out->index));
-    memcpy(out->kind, p->kind, np * sizeof(int));
-    memcpy(out->index, p->index, np * sizeof(int));
+    memcpy(out->kind, p->probes.kind, np * sizeof(int));
+    memcpy(out->index, p->probes.index, np * sizeof(int));
     out->nchains = ncold;
     out->nkept = p->n;
     return 0;
@@ -439,19 +427,6 @@ extern "C" int mceik_mcmc_cov_partials(mceik_mcmc *s, mceik_cov_partials *out)
 
 // ---------------------------------------------------------------------------
 // host only from here: no GPU call
-typedef unsigned __int128 u128;
-typedef __int128 i128;
-
-static i128 get128(const unsigned long long *w) { return (i128)(((u128)w[1] << 64) | w[0]); }
-
-static void add128(unsigned long long *d, const unsigned long long *a, size_t n)
-{
-    for (size_t k = 0; k < n; k++) {
-        const u128 t = (u128)get128(d + 2 * k) + (u128)get128(a + 2 * k);
-        d[2 * k] = (unsigned long long)t;
-        d[2 * k + 1] = (unsigned long long)(t >> 64);
-    }
-}
 
 static bool cov_parts_ok(const mceik_cov_partials *p)
 {
@@ -495,17 +470,17 @@ extern "C" int mceik_cov_finish(const mceik_cov_partials *p, double *cov, double
     std::vector<i128> nx(np), nwx(np), nv(ncm), nwv(ncm);
     std::vector<double> vx(np), wx(np), vv(ncm), wv(ncm);
     for (size_t k = 0; k < np; k++) {
-        const i128 A = p->A[k], G = get128(p->G + 2 * (k * np + k));
+        const i128 A = p->A[k], G = (i128)get128(p->G + 2 * (k * np + k));
         nx[k] = N * G - A * A;
         vx[k] = (double)nx[k] / den;
-        nwx[k] = within ? (i128)n * G - get128(p->PA + 2 * (k * np + k)) : 0;
+        nwx[k] = within ? (i128)n * G - (i128)get128(p->PA + 2 * (k * np + k)) : 0;
         wx[k] = (double)nwx[k] / denw;
     }
     for (size_t j = 0; j < ncm; j++) {
-        const i128 S = p->S[j], Q = get128(p->Q + 2 * j);
+        const i128 S = p->S[j], Q = (i128)get128(p->Q + 2 * j);
         nv[j] = N * Q - S * S;
         vv[j] = (double)nv[j] / den;
-        nwv[j] = within ? (i128)n * Q - get128(p->P + 2 * j) : 0;
+        nwv[j] = within ? (i128)n * Q - (i128)get128(p->P + 2 * j) : 0;
         wv[j] = (double)nwv[j] / denw;
     }
     for (size_t k = 0; k < np; k++) {
@@ -513,21 +488,21 @@ extern "C" int mceik_cov_finish(const mceik_cov_partials *p, double *cov, double
         if (pmean) pmean[k] = N > 0 ? (double)A / dN : NAN;
         for (size_t j = 0; j < ncm; j++) {
             const size_t e = k * ncm + j;
-            const i128 C = get128(p->C + 2 * e);
+            const i128 C = (i128)get128(p->C + 2 * e);
             const double c = pooled ? (double)(N * C - A * (i128)p->S[j]) / den : NAN;
             if (cov) cov[e] = c;
             if (corr) corr[e] = pooled && nx[k] != 0 && nv[j] != 0 ? c / sqrt(vx[k] * vv[j]) : NAN;
-            const double cw = within ? (double)((i128)n * C - get128(p->T + 2 * e)) / denw : NAN;
+            const double cw = within ? (double)((i128)n * C - (i128)get128(p->T + 2 * e)) / denw : NAN;
             if (covw) covw[e] = cw;
             if (corrw) corrw[e] = within && nwx[k] != 0 && nwv[j] != 0 ? cw / sqrt(wx[k] * wv[j]) : NAN;
         }
         for (size_t q = 0; q < np; q++) {
             const size_t e = k * np + q;
-            const i128 G = get128(p->G + 2 * e);
+            const i128 G = (i128)get128(p->G + 2 * e);
             const double c = pooled ? (double)(N * G - A * (i128)p->A[q]) / den : NAN;
             if (pcov) pcov[e] = c;
             if (pcorr) pcorr[e] = pooled && nx[k] != 0 && nx[q] != 0 ? c / sqrt(vx[k] * vx[q]) : NAN;
-            const double cw = within ? (double)((i128)n * G - get128(p->PA + 2 * e)) / denw : NAN;
+            const double cw = within ? (double)((i128)n * G - (i128)get128(p->PA + 2 * e)) / denw : NAN;
             if (pcovw) pcovw[e] = cw;
             if (pcorrw) pcorrw[e] = within && nwx[k] != 0 && nwx[q] != 0 ? cw / sqrt(wx[k] * wx[q]) : NAN;
         }

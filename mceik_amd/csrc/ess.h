@@ -38,11 +38,12 @@ struct EssDev {
 
 struct McmcEss;                    // a sampler's ESS state (ess.hip)
 
-// The step loop's side (sampler.hip mcmc_steps): the n chains of view D / H / N
-// that are chains [chain_off, chain_off + n) of the sampler are added as kept
-// state number t of the chain, k = mcmc_ess_k(p) the trailing zero bits of t
-// (the same for every pipe of a step); once every chain of a kept step is
-// queued, count the state.
+// The kept-state hook's side (sampler.hip kept_queue), in posterior.h's
+// convention: the first n chains of view D / H / N, which are chains
+// [chain_off, chain_off + n) of the sampler, are added as kept state number t
+// of the chain, k = mcmc_ess_k(p) the trailing zero bits of t (it depends on
+// the count alone: the same for every pipe of a step); once every chain of a
+// kept step is queued, count the state.
 int mcmc_ess_k(const McmcEss *p);
 hipError_t mcmc_ess_accumulate(McmcEss *p, const McmcDev &D, const HypoDev &H, const NuisDev &N, int chain_off, int n,
                                int k, hipStream_t st);

@@ -26,9 +26,6 @@
 #define ESS_TILE 64                // entries per block: lane = entry
 #define ESS_SLICE 64               // chains per block: wave w takes chains w, w + 4, ... of the slice
 
-typedef unsigned __int128 u128;
-typedef __int128 i128;
-
 // w (lo, hi) += x modulo 2^128 by two 64-bit vector atomics: the low word
 // first, its carry (the returned old value tells) into the high word.  The
 // adds of one word are serialised, every wrap of the low word is seen by
@@ -156,25 +153,19 @@ struct McmcEss {
     EssDev E;                      // every chain of the sampler
     int nchains;
     long long n;                   // states accumulated per chain
-    int kind[MCEIK_COV_MAX_PROBES], index[MCEIK_COV_MAX_PROBES];
-    int *d_probe;                  // [2][np] kind, index
+    ProbeList probes;
 };
 
 void mcmc_ess_counted(McmcEss *p) { p->n++; }
 
 int mcmc_ess_k(const McmcEss *p) { return __builtin_ctzll((unsigned long long)(p->n + 1)); }
 
-bool mcmc_ess_holds_nuis(const McmcEss *p)
-{
-    for (int k = 0; k < p->E.np; k++)
-        if (p->kind[k] >= 2) return true;
-    return false;
-}
+bool mcmc_ess_holds_nuis(const McmcEss *p) { return probes_hold_nuis(p->probes); }
 
 void mcmc_ess_free(McmcEss *p)
 {
     if (!p) return;
-    void *all[] = {p->d_probe, p->E.Sc, p->E.pend, p->E.A, p->E.Q, p->E.P};
+    void *all[] = {p->probes.d, p->E.Sc, p->E.pend, p->E.A, p->E.Q, p->E.P};
     for (void *q : all)
         if (q) hipFree(q);
     delete p;
@@ -223,10 +214,7 @@ static size_t ess_bytes(const McmcEss *p, int which) { return ess_words(p, which
 
 static bool ess_same(const McmcEss *p, const mceik_ess_opts *o)
 {
-    if (p->E.nlevels != o->nlevels || p->E.np != o->np) return false;
-    for (int k = 0; k < o->np; k++)
-        if (p->kind[k] != o->kind[k] || p->index[k] != o->index[k]) return false;
-    return true;
+    return p->E.nlevels == o->nlevels && probes_same(p->probes, o->np, o->kind, o->index);
 }
 
 extern "C" int mceik_ess_check(int nlevels, long long xmax)
@@ -278,18 +266,12 @@ extern "C" int mceik_mcmc_ess_enable(mceik_mcmc *s, const mceik_ess_opts *o)
     p->E.ne = D.ncm + o->np;
     p->E.pend_stride = (size_t)D.nchains * p->E.ne;
     p->nchains = D.nchains;
-    memcpy(p->kind, o->kind, sizeof(int) * o->np);
-    memcpy(p->index, o->index, sizeof(int) * o->np);
-    const size_t np = o->np;
-    bool ok = hipMalloc((void **)&p->d_probe, (2 * np + 1) * sizeof(int)) == hipSuccess;
+    bool ok = probes_upload(p->probes, o->np, o->kind, o->index);
     for (int a = 0; a < 5 && ok; a++) {
         if (!ess_bytes(p, a)) continue;             // one level: no pend
         ok = hipMalloc(ess_array(p, a), ess_bytes(p, a)) == hipSuccess &&
              hipMemset(*ess_array(p, a), 0, ess_bytes(p, a)) == hipSuccess;
     }
-    if (ok && np)
-        ok = hipMemcpy(p->d_probe, p->kind, np * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
-             hipMemcpy(p->d_probe + np, p->index, np * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
         fprintf(stderr, "mceik_mcmc_ess_enable: out of device memory (%zu B of accumulators)\n",
@@ -297,8 +279,8 @@ extern "C" int mceik_mcmc_ess_enable(mceik_mcmc *s, const mceik_ess_opts *o)
         mcmc_ess_free(p);
         return -1;
     }
-    p->E.kind = p->d_probe;
-    p->E.index = p->d_probe + np;
+    p->E.kind = p->probes.d;
+    p->E.index = p->probes.d + o->np;
     s->ess = p;
     s->ess_on = true;
     return 0;
@@ -382,8 +364,6 @@ extern "C" int mceik_mcmc_ess_partials(mceik_mcmc *s, mceik_ess_partials *out)
 
 // ---------------------------------------------------------------------------
 // host only from here: no GPU call
-static u128 get128(const unsigned long long *w) { return ((u128)w[1] << 64) | w[0]; }
-
 static bool ess_parts_ok(const mceik_ess_partials *p)
 {
     return p && p->ncm >= 0 && p->np >= 0 && p->np <= MCEIK_COV_MAX_PROBES && p->nlevels >= 1 &&
@@ -403,15 +383,10 @@ extern "C" int mceik_ess_merge(mceik_ess_partials *dst, const mceik_ess_partials
     if (!ess_parts_ok(dst) || !ess_parts_ok(src)) return 1;
     if (dst->ncm != src->ncm || dst->np != src->np || dst->nlevels != src->nlevels || dst->nkept != src->nkept) return 1;
     const size_t m = (size_t)dst->nlevels * ((size_t)dst->ncm + dst->np);
-    for (size_t k = 0; k < m; k++) {
+    for (size_t k = 0; k < m; k++)
         dst->A[k] = (long long)((unsigned long long)dst->A[k] + (unsigned long long)src->A[k]);
-        const u128 q = get128(dst->Q + 2 * k) + get128(src->Q + 2 * k);
-        const u128 pp = get128(dst->P + 2 * k) + get128(src->P + 2 * k);
-        dst->Q[2 * k] = (unsigned long long)q;
-        dst->Q[2 * k + 1] = (unsigned long long)(q >> 64);
-        dst->P[2 * k] = (unsigned long long)pp;
-        dst->P[2 * k + 1] = (unsigned long long)(pp >> 64);
-    }
+    add128(dst->Q, src->Q, m);
+    add128(dst->P, src->P, m);
     dst->nchains += src->nchains;
     return 0;
 }

@@ -18,20 +18,11 @@ struct PostDev {
 
 struct McmcPost;                   // a sampler's posterior state (posterior.hip)
 
-// What posterior.hip needs of a sampler (sampler_api.hip fills it).
-struct McmcPostCtx {
-    int device;
-    hipStream_t stream;
-    const McmcDev *D;
-    McmcPost **slot;               // the sampler's posterior pointer (null: off)
-    int ncold;                     // chains the posterior sees: [0, ncold) (parallel tempering: the cold ones)
-};
-int mcmc_post_ctx(mceik_mcmc *s, McmcPostCtx *out);
-
-// The step loop's side (sampler.hip mcmc_steps): add the current models of the
-// chains in view V (chains [chain_off, chain_off + V.nchains) of the sampler)
-// on stream st; once every chain of a kept step is queued, count the state.
-hipError_t mcmc_post_accumulate(McmcPost *p, const McmcDev &V, int chain_off, hipStream_t st);
+// The kept-state hook's side (sampler.hip kept_queue): add the current models
+// of the first n chains of view D, which are chains [chain_off, chain_off + n)
+// of the sampler, on stream st; once every chain of a kept step is queued,
+// count the state.  cov.h and ess.h take their chains the same way.
+hipError_t mcmc_post_accumulate(McmcPost *p, const McmcDev &D, int chain_off, int n, hipStream_t st);
 void mcmc_post_counted(McmcPost *p);
 long long mcmc_post_count(const McmcPost *p);   // states accumulated per chain
 void mcmc_post_free(McmcPost *p);

@@ -18,7 +18,7 @@
 #include "../../include/mceik.h"
 #define HIPCHK_WHO "mceik_posterior"
 #include "host_util.h"
-#include "posterior.h"
+#include "sampler.h"
 
 #define POST_TILE 64               // model entries per block: lane = entry
 #define POST_SLICE 64              // chains per block: wave w takes chains w, w + 4, ... of the slice
@@ -180,9 +180,11 @@ void mcmc_post_counted(McmcPost *p) { p->n++; }
 
 long long mcmc_post_count(const McmcPost *p) { return p->n; }
 
-hipError_t mcmc_post_accumulate(McmcPost *p, const McmcDev &V, int chain_off, hipStream_t st)
+hipError_t mcmc_post_accumulate(McmcPost *p, const McmcDev &D, int chain_off, int n, hipStream_t st)
 {
-    if (V.nchains <= 0) return hipSuccess;
+    if (n <= 0) return hipSuccess;
+    McmcDev V = D;                     // the kernel adds every chain of the view it is given
+    V.nchains = n;
     PostDev A = p->P;
     if (A.per_chain) {
         A.sum += (size_t)chain_off * p->ncm;
@@ -210,24 +212,23 @@ static int post_zero(McmcPost *p, hipStream_t st)
 
 extern "C" int mceik_mcmc_posterior_enable(mceik_mcmc *s, const mceik_posterior_opts *o)
 {
-    McmcPostCtx x;
-    if (!o || mcmc_post_ctx(s, &x)) return 1;
+    if (!s || !o) return 1;
     if (o->nbins < 0 || o->nbins > MCEIK_POST_MAX_BINS) return 1;
-    DeviceScope dg(x.device);
+    DeviceScope dg(s->device);
     const int per_chain = o->per_chain ? 1 : 0;
-    McmcPost *p = *x.slot;
+    McmcPost *p = s->post;
     if (p && (p->P.per_chain != per_chain || p->P.nbins != o->nbins)) {
-        HIPCHK(hipStreamSynchronize(x.stream));
+        HIPCHK(hipStreamSynchronize(s->stream));
         mcmc_post_free(p);
-        *x.slot = p = nullptr;
+        s->post = p = nullptr;
     }
     if (!p) {
         p = new McmcPost();
         memset(p, 0, sizeof(*p));
         p->P.per_chain = per_chain;
         p->P.nbins = o->nbins;
-        p->nchains = x.D->nchains;
-        p->ncm = x.D->ncm;
+        p->nchains = s->D.nchains;
+        p->ncm = s->D.ncm;
         const size_t n = post_rows(p) * p->ncm, m = (size_t)p->ncm;
         if (hipMalloc((void **)&p->P.sum, n * 8) != hipSuccess || hipMalloc((void **)&p->P.sumsq, n * 8) != hipSuccess ||
             (o->nbins && hipMalloc((void **)&p->P.hist, m * o->nbins * 4) != hipSuccess) ||
@@ -239,46 +240,41 @@ extern "C" int mceik_mcmc_posterior_enable(mceik_mcmc *s, const mceik_posterior_
             return -1;
         }
     }
-    if (post_zero(p, x.stream)) {
+    if (post_zero(p, s->stream)) {
         mcmc_post_free(p);
-        *x.slot = nullptr;
+        s->post = nullptr;
         return -1;
     }
-    *x.slot = p;
+    s->post = p;
     return 0;
 }
 
 extern "C" int mceik_mcmc_posterior_disable(mceik_mcmc *s)
 {
-    McmcPostCtx x;
-    if (mcmc_post_ctx(s, &x)) return 1;
-    if (!*x.slot) return 0;
-    DeviceScope dg(x.device);
-    const hipError_t e = hipStreamSynchronize(x.stream);
-    mcmc_post_free(*x.slot);
-    *x.slot = nullptr;
+    if (!s) return 1;
+    if (!s->post) return 0;
+    DeviceScope dg(s->device);
+    const hipError_t e = hipStreamSynchronize(s->stream);
+    mcmc_post_free(s->post);
+    s->post = nullptr;
     return e == hipSuccess ? 0 : -1;
 }
 
 extern "C" int mceik_mcmc_posterior_accumulate(mceik_mcmc *s)
 {
-    McmcPostCtx x;
-    if (mcmc_post_ctx(s, &x) || !*x.slot) return 1;
-    DeviceScope dg(x.device);
-    McmcDev V = *x.D;
-    V.nchains = x.ncold;             // tempering: the hot chains' rows stay zero
-    HIPCHK(mcmc_post_accumulate(*x.slot, V, 0, x.stream));
-    mcmc_post_counted(*x.slot);
+    if (!s || !s->post) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(mcmc_post_accumulate(s->post, s->D, 0, temper_cold(s), s->stream));   // tempering: the hot chains' rows stay zero
+    mcmc_post_counted(s->post);
     return 0;
 }
 
 extern "C" int mceik_mcmc_posterior_get(mceik_mcmc *s, long long *n, long long *sum, long long *sumsq, unsigned *hist)
 {
-    McmcPostCtx x;
-    if (mcmc_post_ctx(s, &x) || !*x.slot) return 1;
-    const McmcPost *p = *x.slot;
+    if (!s || !s->post) return 1;
+    const McmcPost *p = s->post;
     if (mceik_mcmc_sync(s)) return -1;
-    DeviceScope dg(x.device);
+    DeviceScope dg(s->device);
     const size_t m = post_rows(p) * p->ncm;
     if (n) *n = p->n;
     if (sum) HIPCHK(hipMemcpy(sum, p->P.sum, m * 8, hipMemcpyDeviceToHost));
@@ -290,13 +286,12 @@ extern "C" int mceik_mcmc_posterior_get(mceik_mcmc *s, long long *n, long long *
 extern "C" int mceik_mcmc_posterior_set(mceik_mcmc *s, long long n, const long long *sum, const long long *sumsq,
                                         const unsigned *hist)
 {
-    McmcPostCtx x;
-    if (mcmc_post_ctx(s, &x) || !*x.slot) return 1;
-    McmcPost *p = *x.slot;
+    if (!s || !s->post) return 1;
+    McmcPost *p = s->post;
     if (n < 0 || !sum || !sumsq || (p->P.nbins && !hist)) return 1;
-    DeviceScope dg(x.device);
+    DeviceScope dg(s->device);
     const size_t m = post_rows(p) * p->ncm;
-    HIPCHK(hipStreamSynchronize(x.stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
     HIPCHK(hipMemcpy(p->P.sum, sum, m * 8, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(p->P.sumsq, sumsq, m * 8, hipMemcpyHostToDevice));
     if (p->P.nbins) HIPCHK(hipMemcpy(p->P.hist, hist, (size_t)p->ncm * p->P.nbins * 4, hipMemcpyHostToDevice));
@@ -306,19 +301,18 @@ extern "C" int mceik_mcmc_posterior_set(mceik_mcmc *s, long long n, const long l
 
 extern "C" int mceik_mcmc_posterior_partials(mceik_mcmc *s, mceik_posterior_partials *out)
 {
-    McmcPostCtx x;
-    if (!out || mcmc_post_ctx(s, &x) || !*x.slot) return 1;
-    const McmcPost *p = *x.slot;
+    if (!s || !out || !s->post) return 1;
+    const McmcPost *p = s->post;
     if (!out->S || !out->Q || !out->P || (p->P.nbins && !out->hist)) return 1;
-    const int ncm = p->ncm;
+    const int ncm = p->ncm, ncold = temper_cold(s);
     {
-        DeviceScope dg(x.device);
-        hipLaunchKernelGGL(post_reduce_kernel, dim3((ncm + 63) / 64), dim3(64), 0, x.stream, p->P, x.ncold, ncm,
+        DeviceScope dg(s->device);
+        hipLaunchKernelGGL(post_reduce_kernel, dim3((ncm + 63) / 64), dim3(64), 0, s->stream, p->P, ncold, ncm,
                            p->d_S, p->d_Q, p->d_P);
         HIPCHK(hipGetLastError());
     }
     if (mceik_mcmc_sync(s)) return -1;
-    DeviceScope dg(x.device);
+    DeviceScope dg(s->device);
     HIPCHK(hipMemcpy(out->S, p->d_S, (size_t)ncm * 8, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(out->Q, p->d_Q, (size_t)ncm * 16, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(out->P, p->d_P, (size_t)ncm * 16, hipMemcpyDeviceToHost));
@@ -331,18 +325,13 @@ extern "C" int mceik_mcmc_posterior_partials(mceik_mcmc *s, mceik_posterior_part
     out->ncm = ncm;
     out->nbins = p->P.nbins;
     out->per_chain = p->P.per_chain;
-    out->nchains = x.ncold;
+    out->nchains = ncold;
     out->nkept = p->n;
     return 0;
 }
 
 // ---------------------------------------------------------------------------
 // host only from here: no GPU call
-typedef unsigned __int128 u128;
-typedef __int128 i128;
-
-static u128 get128(const unsigned long long *w) { return ((u128)w[1] << 64) | w[0]; }
-
 extern "C" int mceik_posterior_merge(mceik_posterior_partials *dst, const mceik_posterior_partials *src)
 {
     if (!dst || !src || !dst->S || !dst->Q || !dst->P || !src->S || !src->Q || !src->P) return 1;
@@ -350,15 +339,9 @@ extern "C" int mceik_posterior_merge(mceik_posterior_partials *dst, const mceik_
         dst->nkept != src->nkept || dst->ncm < 0 || dst->nbins < 0)
         return 1;
     if (dst->nbins && (!dst->hist || !src->hist)) return 1;
-    for (int i = 0; i < dst->ncm; i++) {
-        dst->S[i] += src->S[i];
-        const u128 q = get128(dst->Q + 2 * (size_t)i) + get128(src->Q + 2 * (size_t)i);
-        const u128 p = get128(dst->P + 2 * (size_t)i) + get128(src->P + 2 * (size_t)i);
-        dst->Q[2 * (size_t)i] = (unsigned long long)q;
-        dst->Q[2 * (size_t)i + 1] = (unsigned long long)(q >> 64);
-        dst->P[2 * (size_t)i] = (unsigned long long)p;
-        dst->P[2 * (size_t)i + 1] = (unsigned long long)(p >> 64);
-    }
+    for (int i = 0; i < dst->ncm; i++) dst->S[i] += src->S[i];
+    add128(dst->Q, src->Q, (size_t)dst->ncm);
+    add128(dst->P, src->P, (size_t)dst->ncm);
     const size_t nh = (size_t)dst->ncm * dst->nbins;
     for (size_t k = 0; k < nh; k++) dst->hist[k] += src->hist[k];
     dst->nchains += src->nchains;

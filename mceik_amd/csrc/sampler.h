@@ -22,16 +22,17 @@
 #define MCEIK_MAX_PIPES 4
 #define MCEIK_ITERS_N (6 + MCEIK_TRAFFIC_N)   // d_iters: iterations, 4 visit statistics, solves, traffic
 
-// A pipe: a part of the chains stepped on a stream of its own.  D, B, P, H, N, C, L, fb
+// A pipe: a part of the chains stepped on a stream of its own.  D, B, P, H, N, L, fb
 // and fb_hyp are views of the sampler's restricted to the pipe's chains;
-// pipes_refresh alone writes them.
+// pipes_refresh alone writes them.  (The accumulators of kept states --
+// posterior, covariances, batch means -- have no views: their accumulate calls
+// take the pipe's chain offset.)
 struct Pipe {
     McmcDev D;
     BlockDev B;
     PriorDev P;
     HypoDev H;
     NuisDev N;
-    CovDev C;                          // (all null while the sampler holds no covariance accumulators)
     LangDev L;                         // (arrays null before the first lang_enable)
     mceik_fsm_batch fb;
     mceik_fsm_batch fb_hyp;            // a hypocentre step's batch (every model of the pipe's chains)
@@ -82,8 +83,8 @@ struct mceik_mcmc {
     McmcPost *post;                    // streaming posterior accumulators (posterior.hip), or null
     // Parallel tempering (temper.hip); ntemps = 0: off.  Rung r
     // of replica group g is chain r * G + g (G = nchains / ntemps), so the cold
-    // chains are [0, G).  Before the proposal of step gs > 0 with gs %
-    // swap_every == 0 a swap round of parity (gs / swap_every) & 1 runs.
+    // chains are [0, G).  plan_step (sampler.hip) says which steps a swap round
+    // precedes, and its parity.
     int ntemps, swap_every;
     std::vector<double> beta;          // the ladder [ntemps]
     double *d_beta;                    // [nchains] the chains' beta (D.beta while ntemps > 1)
@@ -107,8 +108,8 @@ struct mceik_mcmc {
     // null until the first enable, which starts every chain at the catalogue's
     // snapped nodes (ev_host) and switches fb / fb_all to per-chain event lists
     // (ev_stride); the positions then stay per chain, also after disable.
-    // While on, every step takes the per-step branch; global step gs is a
-    // hypocentre step iff gs % hypo_every == hypo_every - 1.
+    // While on, every step takes the per-step branch; plan_step says which
+    // steps are hypocentre steps.
     bool hypo_on;
     int hypo_every;
     HypoDev H;
@@ -122,8 +123,7 @@ struct mceik_mcmc {
     // is set the sampler holds nuisance state, every step takes the per-step
     // branch, every logL honours the state, and a one-model sampler keeps its
     // current tables too (D.ttab_cur = ttab_cur1, which the full forward then
-    // fills).  Global step gs is a nuisance step iff nuis_on and gs %
-    // nuis_every == nuis_offset and it is no hypocentre step.
+    // fills).  plan_step says which steps are nuisance steps.
     bool nuis_on;
     int nuis_every, nuis_offset;
     NuisDev N;
@@ -149,8 +149,7 @@ struct mceik_mcmc {
     // uses: the per-chain arrays, and per pipe (lang_pipe) the fields, the
     // workspaces of the forward with fields and of the adjoint, and the pick
     // weights, sized to lang_mem.  While on, every step takes the per-step
-    // branch; global step gs is a Langevin step iff gs % lang_every ==
-    // lang_offset and it is neither a hypocentre nor a nuisance step.
+    // branch; plan_step says which steps are Langevin steps.
     bool lang_on;
     int lang_every, lang_offset;
     double lang_sigma;
@@ -188,11 +187,22 @@ int mcmc_forward_all(mceik_mcmc *s);
 int check_forward_ierr(mceik_mcmc *s, const char *who);
 int temper_cold(const mceik_mcmc *s);
 int temper_round(mceik_mcmc *s, int parity);
+// The sampler runs multi-step launches now.  It was built for them (persist:
+// one pipe), and no feature that needs a launch per step is on: block
+// proposals (the multi-step kernel's epilogue is single-cell); the prior (its
+// fold sits between a step's proposal and its forward); hypocentre moves (a
+// hypocentre step has kernels and a batch of its own); held nuisance state (it
+// enters every logL, which the multi-step kernel's epilogue does not know);
+// Langevin moves (a Langevin step is a pipeline of launches of its own).
+static inline bool mcmc_multi_step(const mceik_mcmc *s)
+{
+    return s->persist && !s->block_on && !s->prior_on && !s->hypo_on && !s->N.kn && !s->lang_on;
+}
 // Bytes pipe k's Langevin step needs for chunks of m chains: the fields (u), the
 // workspaces of the forward with fields (fws) and of the adjoint (aws), the
 // pick weights (evw) and the adjoint's per-solve rows (gs), each a multiple of
 // 256; returns their sum.
 size_t lang_pipe_bytes(const mceik_mcmc *s, int k, int m, size_t *u, size_t *fws, size_t *aws, size_t *evw, size_t *gs);
-// Recomputes every pipe's D, B, P, H, N, C, L and fb from the sampler's (and a multi-step
-// sampler's device copy of D): call after any change to s->D, s->B, s->P, s->cov or s->fb.
+// Recomputes every pipe's D, B, P, H, N, L and fb from the sampler's (and a multi-step
+// sampler's device copy of D): call after any change to s->D, s->B, s->P, s->H, s->N, s->L or s->fb.
 int pipes_refresh(mceik_mcmc *s);

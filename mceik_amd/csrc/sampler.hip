@@ -190,17 +190,6 @@ static NuisDev dev_view(const NuisDev &N, const McmcDev &D, int off)
     return V;
 }
 
-// The same view of the covariance accumulators' per-chain arrays (the pooled sums are the sampler's).
-static CovDev dev_view(const CovDev &C, int off)
-{
-    CovDev V = C;
-    const size_t o = (size_t)off;
-    if (V.X) V.X += o * C.np;
-    if (V.Ac) V.Ac += o * C.np;
-    if (V.Sc) V.Sc += o * C.ncm;
-    return V;
-}
-
 // The same view of the Langevin state's per-chain arrays.
 static LangDev dev_view(const LangDev &L, const McmcDev &D, int off)
 {
@@ -264,7 +253,6 @@ int pipes_refresh(mceik_mcmc *s)
         p.fb = batch_view(s->fb, lo, n, (size_t)s->D.ncm);
         p.H = dev_view(s->H, s->D, lo);
         p.N = dev_view(s->N, s->D, lo);
-        p.C = s->cov ? dev_view(mcmc_cov_dev(s->cov), lo) : CovDev();
         p.L = dev_view(s->L, s->D, lo);
         if (s->H.hyp) p.fb_hyp = hyp_batch_view(s->fb_hyp, p.fb, lo, n, (size_t)s->D.ncm, s->D.nphase);
     }
@@ -687,51 +675,17 @@ static bool kept_step(const mceik_mcmc *s, long long gs)
     return gs >= s->nburn && (gs - s->nburn) % s->keepk == 0;
 }
 
-// Chains the streaming posterior sees: the cold ones while tempering is on.
+// Chains the consumers of a kept state see: the cold ones while tempering is on.
 int temper_cold(const mceik_mcmc *s) { return s->ntemps > 0 ? s->D.nchains / s->ntemps : s->D.nchains; }
+
+// How many of chains [off, off + n) are cold: the first chains of a pipe's view.
+static int cold_in(const mceik_mcmc *s, int off, int n) { return std::max(0, std::min(n, temper_cold(s) - off)); }
 
 static long long next_kept_step(const mceik_mcmc *s)     // the first kept step >= s->step
 {
     if (s->step < s->nburn) return s->nburn;
     const long long r = (s->step - s->nburn) % s->keepk;
     return r ? s->step + s->keepk - r : s->step;
-}
-
-// The posterior sees the cold chains only: view V (chains [off, off +
-// V.nchains) of the sampler) intersected with [0, G).
-static hipError_t post_add(mceik_mcmc *s, const McmcDev &V, int off, hipStream_t st)
-{
-    const int G = temper_cold(s);
-    if (off >= G) return hipSuccess;
-    if (off + V.nchains <= G) return mcmc_post_accumulate(s->post, V, off, st);
-    McmcDev W = V;
-    W.nchains = G - off;
-    return mcmc_post_accumulate(s->post, W, off, st);
-}
-
-// The covariance accumulators see the cold chains only, as the posterior does
-// (post_add): the first chains of pipe p's view (chains [off, ...) of the sampler).
-static hipError_t cov_add(mceik_mcmc *s, const Pipe &p, int off, hipStream_t st)
-{
-    const int G = temper_cold(s);
-    if (off >= G) return hipSuccess;
-    return mcmc_cov_accumulate(p.C, p.D, p.H, p.N, std::min(p.D.nchains, G - off), st);
-}
-
-// The batch-means accumulators see the cold chains only, as the posterior does
-// (post_add): the first chains of pipe p's view (chains [off, ...) of the
-// sampler), added as the kept state whose trailing zero bits are k.
-static hipError_t ess_add(mceik_mcmc *s, const Pipe &p, int off, int k, hipStream_t st)
-{
-    const int G = temper_cold(s);
-    if (off >= G) return hipSuccess;
-    return mcmc_ess_accumulate(s->ess, p.D, p.H, p.N, off, std::min(p.D.nchains, G - off), k, st);
-}
-
-// A swap round belongs to step gs and runs before its proposal.
-static bool swap_step(const mceik_mcmc *s, long long gs)
-{
-    return s->ntemps > 1 && s->swap_every > 0 && gs > 0 && gs % s->swap_every == 0;
 }
 
 int temper_round(mceik_mcmc *s, int parity)
@@ -742,40 +696,59 @@ int temper_round(mceik_mcmc *s, int parity)
     return 0;
 }
 
-// Global step gs moves hypocentres instead of proposing a velocity.
-static bool hypo_step(const mceik_mcmc *s, long long gs)
+// What global step gs is.  A step has one kind, by precedence: hypocentre (gs %
+// hypo_every == hypo_every - 1), else nuisance (gs % nuis_every == nuis_offset
+// while state is held), else Langevin (gs % lang_every == lang_offset), else a
+// velocity proposal.  A swap round belongs to step gs > 0 with gs % swap_every
+// == 0 and runs before its proposal, with parity (gs / swap_every) & 1.
+enum StepKind { STEP_VELOCITY, STEP_HYPO, STEP_NUIS, STEP_LANG };
+
+struct StepPlan {
+    StepKind kind;
+    bool swap;
+    int parity;
+    bool kept;                         // kept_step(gs)
+};
+
+static StepPlan plan_step(const mceik_mcmc *s, long long gs)
 {
-    return s->hypo_on && s->hypo_every > 0 && gs % s->hypo_every == s->hypo_every - 1;
+    StepPlan q;
+    if (s->hypo_on && s->hypo_every > 0 && gs % s->hypo_every == s->hypo_every - 1) q.kind = STEP_HYPO;
+    else if (s->nuis_on && s->N.kn && s->nuis_every > 0 && gs % s->nuis_every == s->nuis_offset) q.kind = STEP_NUIS;
+    else if (s->lang_on && s->lang_every > 0 && gs % s->lang_every == s->lang_offset) q.kind = STEP_LANG;
+    else q.kind = STEP_VELOCITY;
+    q.swap = s->ntemps > 1 && s->swap_every > 0 && gs > 0 && gs % s->swap_every == 0;
+    q.parity = q.swap ? (int)((gs / s->swap_every) & 1) : 0;
+    q.kept = kept_step(s, gs);
+    return q;
 }
 
-// The moments see the cold chains only, as the posterior does (post_add).
-static hipError_t hypo_add(mceik_mcmc *s, const McmcDev &V, const HypoDev &H, int off, hipStream_t st)
+// The kept-state hook.  Five consumers see the cold chains of a kept step:
+// posterior, hypocentre moments, nuisance moments, covariances, batch means.
+// kept_queue queues those that are on for the cold chains of pipe p's view on
+// stream st; kept_counted counts the state on the host once every pipe is
+// queued (mcmc_ess_k depends on that count alone, so every pipe reads the
+// same k).  One pipe views every chain, so the multi-step branch calls the
+// same two, where mcmc_multi_step rules the hypocentre and nuisance moments out.
+static int kept_queue(mceik_mcmc *s, const Pipe &p, hipStream_t st)
 {
-    const int G = temper_cold(s);
-    if (off >= G) return hipSuccess;
-    return hypo_moments(V, H, std::min(V.nchains, G - off), st);
+    const int off = p.D.chain_offset - s->D.chain_offset, n = cold_in(s, off, p.D.nchains);
+    if (n <= 0) return 0;
+    if (s->post) HIPCHK(mcmc_post_accumulate(s->post, p.D, off, n, st));
+    if (s->hypo_on) HIPCHK(hypo_moments(p.D, p.H, n, st));
+    if (s->nuis_on && s->N.kn) HIPCHK(nuis_moments(p.D, p.N, n, st));
+    if (s->cov_on) HIPCHK(mcmc_cov_accumulate(s->cov, p.D, p.H, p.N, off, n, st));
+    if (s->ess_on) HIPCHK(mcmc_ess_accumulate(s->ess, p.D, p.H, p.N, off, n, mcmc_ess_k(s->ess), st));
+    return 0;
 }
 
-// Global step gs runs the noise / statics sub-moves instead of proposing a
-// velocity (a step that is also a hypocentre step is a hypocentre step).
-static bool nuis_is_step(const mceik_mcmc *s, long long gs)
+static void kept_counted(mceik_mcmc *s)
 {
-    return s->nuis_on && s->N.kn && s->nuis_every > 0 && gs % s->nuis_every == s->nuis_offset;
-}
-
-// The moments see the cold chains only, as the posterior does (post_add).
-static hipError_t nuis_add(mceik_mcmc *s, const McmcDev &V, const NuisDev &N, int off, hipStream_t st)
-{
-    const int G = temper_cold(s);
-    if (off >= G) return hipSuccess;
-    return nuis_moments(V, N, std::min(V.nchains, G - off), st);
-}
-
-// Global step gs is a Langevin step in place of a velocity proposal (the caller
-// has ruled out a hypocentre and a nuisance step).
-static bool lang_is_step(const mceik_mcmc *s, long long gs)
-{
-    return s->lang_on && s->lang_every > 0 && gs % s->lang_every == s->lang_offset;
+    if (s->post) mcmc_post_counted(s->post);
+    if (s->hypo_on) s->hyp_n += temper_cold(s);
+    if (s->nuis_on && s->N.kn) s->nuis_n += temper_cold(s);
+    if (s->cov_on) mcmc_cov_counted(s->cov);
+    if (s->ess_on) mcmc_ess_counted(s->ess);
 }
 
 // Chains [off, off + m) of pipe p's step batch as a Langevin step runs them:
@@ -870,13 +843,7 @@ static int lang_step(mceik_mcmc *s, int k, uint64_t step, int slot)
 // kernel this call queued on the internal streams.
 static int mcmc_steps(mceik_mcmc *s, int nsteps)
 {
-    // block proposals: the multi-step kernel's epilogue is single-cell, so a
-    // sampler built for multi-step launches (one pipe) steps per launch; the
-    // prior's fold sits between a step's proposal and its forward, likewise;
-    // a hypocentre step has kernels and a batch of its own; nuisance state
-    // enters every logL, which the multi-step kernel's epilogue does not know;
-    // a Langevin step is a pipeline of launches of its own
-    if (s->persist && !s->block_on && !s->prior_on && !s->hypo_on && !s->N.kn && !s->lang_on) {
+    if (mcmc_multi_step(s)) {
         // the first step's proposals here, then up to MCEIK_MC_CHUNK steps per
         // FSM launch (the kernel accepts, keeps and proposes the rest)
         for (int done = 0; done < nsteps;) {
@@ -885,7 +852,8 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
             // kept step, when every chain's current state is its state after that step
             if (s->post || s->cov_on || s->ess_on) n = (int)std::min<long long>(n, next_kept_step(s) - s->step + 1);
             // tempering: this step's swap round first; the launch ends before the next one
-            if (swap_step(s, s->step) && temper_round(s, (int)((s->step / s->swap_every) & 1))) return -1;
+            const StepPlan q = plan_step(s, s->step);         // (a velocity step: mcmc_multi_step)
+            if (q.swap && temper_round(s, q.parity)) return -1;
             if (s->ntemps > 1 && s->swap_every > 0)
                 n = (int)std::min<long long>(n, (s->step / s->swap_every + 1) * s->swap_every - s->step);
             McmcExt x;
@@ -895,18 +863,10 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
             HIPCHK(mcmc_propose(s->D, (uint64_t)s->step, s->stream));
             if (mcmc_forward(s, true, 0, &x)) return -1;
             for (int i = 0; i < n; i++, s->step++)
-                if (s->max_samples && s->step >= s->nburn && (s->step - s->nburn) % s->keepk == 0) s->nkept++;
-            if (s->post && kept_step(s, s->step - 1)) {
-                HIPCHK(post_add(s, s->D, 0, s->stream));
-                mcmc_post_counted(s->post);
-            }
-            if (s->cov_on && kept_step(s, s->step - 1)) {
-                HIPCHK(cov_add(s, s->pipe[0], 0, s->stream));      // one pipe: it views every chain
-                mcmc_cov_counted(s->cov);
-            }
-            if (s->ess_on && kept_step(s, s->step - 1)) {
-                HIPCHK(ess_add(s, s->pipe[0], 0, mcmc_ess_k(s->ess), s->stream));
-                mcmc_ess_counted(s->ess);
+                if (s->max_samples && kept_step(s, s->step)) s->nkept++;
+            if (kept_step(s, s->step - 1)) {                   // one pipe: it views every chain
+                if (kept_queue(s, s->pipe[0], s->stream)) return -1;
+                kept_counted(s);
             }
             if (s->report) clock_report(s, "steps");
             done += n;
@@ -918,25 +878,19 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
     for (int i = 0; i < nsteps; i++) {
         uint64_t step = (uint64_t)s->step;
         int slot = -1;
-        const bool post = s->post && kept_step(s, s->step);
-        const bool cov = s->cov_on && kept_step(s, s->step);
-        const bool ess = s->ess_on && kept_step(s, s->step);
-        const int ess_k = ess ? mcmc_ess_k(s->ess) : 0;      // the same for every pipe of the step
-        const bool hstep = hypo_step(s, s->step), hmom = s->hypo_on && kept_step(s, s->step);
-        const bool nstep = !hstep && nuis_is_step(s, s->step), nmom = s->nuis_on && s->N.kn && kept_step(s, s->step);
-        const bool lstep = !hstep && !nstep && lang_is_step(s, s->step);
-        if (s->max_samples && s->step >= s->nburn && (s->step - s->nburn) % s->keepk == 0) {
+        const StepPlan q = plan_step(s, s->step);
+        if (s->max_samples && q.kept) {
             slot = s->nkept % s->max_samples;
             s->nkept++;
         }
-        if (swap_step(s, s->step)) {
+        if (q.swap) {
             // one round for the whole sampler on its own stream: the pipes join it
             // and fork again (their split need not fall on a group boundary)
             for (int k = 0; k < np && np > 1; k++) {
                 HIPCHK(hipEventRecord(s->pipe[k].join, s->pipe[k].st));
                 HIPCHK(hipStreamWaitEvent(s->stream, s->pipe[k].join, 0));
             }
-            if (temper_round(s, (int)((s->step / s->swap_every) & 1))) return -1;
+            if (temper_round(s, q.parity)) return -1;
             if (np > 1) {
                 HIPCHK(hipEventRecord(s->pfork, s->stream));
                 for (int k = 0; k < np; k++) HIPCHK(hipStreamWaitEvent(s->pipe[k].st, s->pfork, 0));
@@ -945,32 +899,28 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
         for (int k = 0; k < np; k++) {
             const Pipe &p = s->pipe[k];
             const hipStream_t st = pipe_stream(s, k);
-            if (hstep) {            // every event of every chain moves on one forward of the current models
+            switch (q.kind) {
+            case STEP_HYPO:         // every event of every chain moves on one forward of the current models
                 HIPCHK(hypo_propose(p.D, p.H, step, st));
                 if (mcmc_forward(s, true, k, nullptr, true)) return -1;
                 HIPCHK(hypo_accept(p.D, p.H, p.N, slot, st));
-            } else if (nstep) {     // nsub sub-moves per chain from the tables the chain holds: no forward
+                break;
+            case STEP_NUIS:         // nsub sub-moves per chain from the tables the chain holds: no forward
                 HIPCHK(nuis_step(p.D, p.N, step, slot, st));
-            } else if (lstep) {     // every cell of one model moves along its gradient: two forwards, two adjoints
+                break;
+            case STEP_LANG:         // every cell of one model moves along its gradient: two forwards, two adjoints
                 if (lang_step(s, k, step, slot)) return -1;
-            } else {
+                break;
+            case STEP_VELOCITY:
                 HIPCHK(blk ? block_propose(p.D, p.B, step, st) : mcmc_propose(p.D, step, st));
                 if (s->prior_on) HIPCHK(prior_fold(p.D, p.B, p.P, blk, st));
                 if (mcmc_forward(s, true, k)) return -1;
                 HIPCHK(blk ? block_accept(p.D, p.B, p.N, slot, st) : mcmc_accept(p.D, p.N, slot, st));
+                break;
             }
-            if (post)               // the pipe's rows of the accumulators, offset like its keep_v (dev_view)
-                HIPCHK(post_add(s, p.D, p.D.chain_offset - s->D.chain_offset, st));
-            if (hmom) HIPCHK(hypo_add(s, p.D, p.H, p.D.chain_offset - s->D.chain_offset, st));
-            if (nmom) HIPCHK(nuis_add(s, p.D, p.N, p.D.chain_offset - s->D.chain_offset, st));
-            if (cov) HIPCHK(cov_add(s, p, p.D.chain_offset - s->D.chain_offset, st));
-            if (ess) HIPCHK(ess_add(s, p, p.D.chain_offset - s->D.chain_offset, ess_k, st));
+            if (q.kept && kept_queue(s, p, st)) return -1;
         }
-        if (post) mcmc_post_counted(s->post);
-        if (cov) mcmc_cov_counted(s->cov);
-        if (ess) mcmc_ess_counted(s->ess);
-        if (hmom) s->hyp_n += temper_cold(s);
-        if (nmom) s->nuis_n += temper_cold(s);
+        if (q.kept) kept_counted(s);
         if (s->report) clock_report(s, "step");
         s->step++;
     }

@@ -21,6 +21,35 @@
 #include "mcmc_host.h"
 #include "sampler.h"
 
+// The posterior holds states: a change of what the chains sample is refused.
+static bool post_holds_states(const mceik_mcmc *s) { return s->post && mcmc_post_count(s->post) > 0; }
+
+// The body of the *_stats entry points: n words of each counter array to the
+// host (synchronises), then with reset nreset zero words from `zero` on.
+static int get_counts(mceik_mcmc *s, const unsigned long long *att, const unsigned long long *acc, size_t n,
+                      long long *attempts, long long *accepts, int reset, unsigned long long *zero, size_t nreset)
+{
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    if (attempts && n) HIPCHK(hipMemcpy(attempts, att, n * 8, hipMemcpyDeviceToHost));
+    if (accepts && n) HIPCHK(hipMemcpy(accepts, acc, n * 8, hipMemcpyDeviceToHost));
+    if (reset) HIPCHK(hipMemset(zero, 0, nreset * 8));
+    return 0;
+}
+
+// One forward of every model of every chain at the chains' positions, and
+// logL from it (not timed, not counted in the FSM stats).  Synchronises.
+static int forward_logl(mceik_mcmc *s, const char *who)
+{
+    unsigned long long keep[MCEIK_ITERS_N];
+    HIPCHK(hipMemcpy(keep, s->d_iters, sizeof(keep), hipMemcpyDeviceToHost));
+    if (mcmc_forward_all(s)) return -1;
+    HIPCHK(mcmc_init_loglik(s->D, s->N, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    HIPCHK(hipMemcpy(s->d_iters, keep, sizeof(keep), hipMemcpyHostToDevice));
+    return check_forward_ierr(s, who) ? 2 : 0;
+}
+
 // ---------------------------------------------------------------------------
 // parallel tempering (include/mceik.h mceik_mcmc_temper_*)
 
@@ -39,7 +68,7 @@ extern "C" int mceik_mcmc_temper_enable(mceik_mcmc *s, const mceik_temper_opts *
     if (nch % nt != 0 || o->beta[0] != 1.0) return 1;
     for (int r = 0; r + 1 < nt; r++)
         if (!(o->beta[r + 1] > 0.0 && o->beta[r + 1] <= o->beta[r])) return 1;
-    if (s->post && mcmc_post_count(s->post) > 0) return 1;
+    if (post_holds_states(s)) return 1;
     DeviceScope dg(s->device);
     HIPCHK(hipStreamSynchronize(s->stream));
     if (!s->d_beta && (dalloc(s, &s->d_beta, nch) || dalloc(s, &s->d_tflag, nch) || dalloc(s, &s->d_tcnt, 2 * (size_t)nch)))
@@ -60,7 +89,7 @@ extern "C" int mceik_mcmc_temper_disable(mceik_mcmc *s)
 {
     if (!s) return 1;
     if (!s->ntemps) return 0;
-    if (s->post && mcmc_post_count(s->post) > 0) return 1;
+    if (post_holds_states(s)) return 1;
     DeviceScope dg(s->device);
     HIPCHK(hipStreamSynchronize(s->stream));
     s->ntemps = 0;
@@ -82,13 +111,8 @@ extern "C" int mceik_mcmc_temper_get(mceik_mcmc *s, int *ntemps, int *swap_every
 extern "C" int mceik_mcmc_temper_stats(mceik_mcmc *s, long long *attempts, long long *accepts, int reset)
 {
     if (!s || !s->ntemps) return 1;
-    DeviceScope dg(s->device);
-    HIPCHK(hipStreamSynchronize(s->stream));
-    const size_t n = (size_t)(s->ntemps - 1) * 8;
-    if (attempts && n) HIPCHK(hipMemcpy(attempts, s->d_tcnt, n, hipMemcpyDeviceToHost));
-    if (accepts && n) HIPCHK(hipMemcpy(accepts, s->d_tcnt + s->D.nchains, n, hipMemcpyDeviceToHost));
-    if (reset) HIPCHK(hipMemset(s->d_tcnt, 0, 2 * (size_t)s->D.nchains * 8));
-    return 0;
+    return get_counts(s, s->d_tcnt, s->d_tcnt + s->D.nchains, (size_t)s->ntemps - 1, attempts, accepts, reset, s->d_tcnt,
+                      2 * (size_t)s->D.nchains);
 }
 
 extern "C" int mceik_mcmc_temper_swap(mceik_mcmc *s, int parity)
@@ -144,14 +168,8 @@ extern "C" int mceik_mcmc_block_get(mceik_mcmc *s, int *rmin, int *rmax)
 extern "C" int mceik_mcmc_block_stats(mceik_mcmc *s, long long *attempts, long long *accepts, int reset)
 {
     if (!s || !s->block_on) return 1;
-    DeviceScope dg(s->device);
-    HIPCHK(hipStreamSynchronize(s->stream));
-    const int nr = MCEIK_BLOCK_RMAX + 1;
-    const size_t n = (size_t)(s->B.rmax + 1) * 8;
-    if (attempts) HIPCHK(hipMemcpy(attempts, s->B.attempts, n, hipMemcpyDeviceToHost));
-    if (accepts) HIPCHK(hipMemcpy(accepts, s->B.accepts, n, hipMemcpyDeviceToHost));
-    if (reset) HIPCHK(hipMemset(s->d_bcnt, 0, 2 * (size_t)nr * 8));
-    return 0;
+    return get_counts(s, s->B.attempts, s->B.accepts, (size_t)s->B.rmax + 1, attempts, accepts, reset, s->d_bcnt,
+                      2 * (size_t)(MCEIK_BLOCK_RMAX + 1));
 }
 
 extern "C" int mceik_block_footprint(int ncx, int ncy, int ncz, int cell, int radius, int amp, int *cells, int *dv)
@@ -201,7 +219,7 @@ extern "C" int mceik_mcmc_prior_enable(mceik_mcmc *s, const mceik_prior_opts *o)
                 return 1;
             }
         }
-    if (s->post && mcmc_post_count(s->post) > 0) return 1;
+    if (post_holds_states(s)) return 1;
     DeviceScope dg(s->device);
     HIPCHK(hipStreamSynchronize(s->stream));
     const int nch = D.nchains;
@@ -229,7 +247,7 @@ extern "C" int mceik_mcmc_prior_disable(mceik_mcmc *s)
 {
     if (!s) return 1;
     if (!s->prior_on) return 0;
-    if (s->post && mcmc_post_count(s->post) > 0) return 1;
+    if (post_holds_states(s)) return 1;
     s->prior_on = false;               // host state only: queued steps keep the kernels they were queued with
     return 0;
 }
@@ -324,8 +342,6 @@ extern "C" int mceik_prior_delta(int ncx, int ncy, int ncz, const int *v, const 
 // ---------------------------------------------------------------------------
 // hypocentre moves (include/mceik.h mceik_mcmc_hypo_*)
 
-static int forward_logl(mceik_mcmc *s, const char *who);
-
 static bool hypo_in(const int *q, const int *lo, const int *hi)
 {
     return q[0] >= lo[0] && q[0] <= hi[0] && q[1] >= lo[1] && q[1] <= hi[1] && q[2] >= lo[2] && q[2] <= hi[2];
@@ -354,7 +370,7 @@ extern "C" int mceik_mcmc_hypo_enable(mceik_mcmc *s, const mceik_hypo_opts *o)
         fprintf(stderr, "mceik_mcmc_hypo_enable: hypocentres move by whole nodes; not with tt_interp = 1\n");
         return 1;
     }
-    if (s->post && mcmc_post_count(s->post) > 0) return 1;
+    if (post_holds_states(s)) return 1;
     DeviceScope dg(s->device);
     HIPCHK(hipStreamSynchronize(s->stream));
     const int nch = D.nchains, nev = D.nev, nph = D.nphase;
@@ -458,13 +474,8 @@ extern "C" int mceik_mcmc_hypo_set(mceik_mcmc *s, const int *xyz)
 extern "C" int mceik_mcmc_hypo_stats(mceik_mcmc *s, long long *attempts, long long *accepts, int reset)
 {
     if (!s || !s->H.hyp) return 1;
-    DeviceScope dg(s->device);
-    HIPCHK(hipStreamSynchronize(s->stream));
-    const size_t n = (size_t)s->D.nev * 8;
-    if (attempts) HIPCHK(hipMemcpy(attempts, s->H.attempts, n, hipMemcpyDeviceToHost));
-    if (accepts) HIPCHK(hipMemcpy(accepts, s->H.accepts, n, hipMemcpyDeviceToHost));
-    if (reset) HIPCHK(hipMemset(s->d_hcnt, 0, 2 * n));
-    return 0;
+    const size_t n = s->D.nev;
+    return get_counts(s, s->H.attempts, s->H.accepts, n, attempts, accepts, reset, s->d_hcnt, 2 * n);
 }
 
 extern "C" int mceik_mcmc_hypo_last(mceik_mcmc *s, int *cand, unsigned char *accept, double *obj)
@@ -574,7 +585,7 @@ extern "C" int mceik_mcmc_nuis_enable(mceik_mcmc *s, const mceik_nuis_opts *o)
         if (!(fabs(norm[ph]) <= DBL_MAX)) return 1;
     }
     if ((noise ? nph : 0) + nact[0] + nact[1] == 0) return 1;
-    if (s->post && mcmc_post_count(s->post) > 0) return 1;
+    if (post_holds_states(s)) return 1;
     // MCEIK_NUIS_LDS (test hook): fewer bytes of LDS for a nuisance step's block, so that small problems take
     // the path without the staged travel times
     size_t lds_max = MCEIK_NUIS_LDS_MAX;
@@ -678,7 +689,7 @@ extern "C" int mceik_mcmc_nuis_clear(mceik_mcmc *s)
 {
     if (!s) return 1;
     if (!s->N.kn) return 0;
-    if (s->post && mcmc_post_count(s->post) > 0) return 1;
+    if (post_holds_states(s)) return 1;
     if (s->cov_on && mcmc_cov_holds_nuis(s->cov)) return 1;   // a registered probe reads the values
     if (s->ess_on && mcmc_ess_holds_nuis(s->ess)) return 1;   // likewise
     DeviceScope dg(s->device);
@@ -740,13 +751,8 @@ extern "C" int mceik_mcmc_nuis_set(mceik_mcmc *s, const int *kn, const int *kc)
 extern "C" int mceik_mcmc_nuis_stats(mceik_mcmc *s, long long *attempts, long long *accepts, int reset)
 {
     if (!s || !s->N.kn) return 1;
-    DeviceScope dg(s->device);
-    HIPCHK(hipStreamSynchronize(s->stream));
-    const size_t n = nuis_npar(s->D) * 8;
-    if (attempts) HIPCHK(hipMemcpy(attempts, s->N.attempts, n, hipMemcpyDeviceToHost));
-    if (accepts) HIPCHK(hipMemcpy(accepts, s->N.accepts, n, hipMemcpyDeviceToHost));
-    if (reset) HIPCHK(hipMemset(s->N.attempts, 0, 2 * n));
-    return 0;
+    const size_t n = nuis_npar(s->D);
+    return get_counts(s, s->N.attempts, s->N.accepts, n, attempts, accepts, reset, s->N.attempts, 2 * n);
 }
 
 extern "C" int mceik_mcmc_nuis_last(mceik_mcmc *s, int *rec, double *logl)
@@ -966,17 +972,6 @@ extern "C" int mceik_lang_cell(uint32_t seed, uint32_t gchain, uint64_t step, in
     return 0;
 }
 
-int mcmc_post_ctx(mceik_mcmc *s, McmcPostCtx *out)
-{
-    if (!s || !out) return 1;
-    out->device = s->device;
-    out->stream = s->stream;
-    out->D = &s->D;
-    out->slot = &s->post;
-    out->ncold = temper_cold(s);
-    return 0;
-}
-
 // After a stream synchronisation: a multi-step launch whose wave gave up
 // waiting for a chain's step (the broken-queue flag) failed, and the chains'
 // state is not to be trusted; every later synchronising call (and the
@@ -1022,19 +1017,6 @@ extern "C" int mceik_mcmc_checkpoint(mceik_mcmc *s, int *v, double *logl, long l
     if (mceik_mcmc_get_state(s, v, logl, naccept, step)) return -1;
     if (nkept) *nkept = s->nkept;
     return 0;
-}
-
-// One forward of every model of every chain at the chains' positions, and
-// logL from it (not timed, not counted in the FSM stats).  Synchronises.
-static int forward_logl(mceik_mcmc *s, const char *who)
-{
-    unsigned long long keep[MCEIK_ITERS_N];
-    HIPCHK(hipMemcpy(keep, s->d_iters, sizeof(keep), hipMemcpyDeviceToHost));
-    if (mcmc_forward_all(s)) return -1;
-    HIPCHK(mcmc_init_loglik(s->D, s->N, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    HIPCHK(hipMemcpy(s->d_iters, keep, sizeof(keep), hipMemcpyHostToDevice));
-    return check_forward_ierr(s, who) ? 2 : 0;
 }
 
 extern "C" int mceik_mcmc_restore(mceik_mcmc *s, const int *v, const double *logl, const long long *naccept,
@@ -1150,8 +1132,7 @@ extern "C" int mceik_mcmc_get_info(mceik_mcmc *s, mceik_mcmc_info *info)
     DeviceScope dg(s->device);
     memset(info, 0, sizeof(*info));
     info->npipe = s->npipe;
-    // block proposals, the prior, hypocentre moves, nuisance state and Langevin moves step per launch
-    info->multi_step = s->persist && !s->block_on && !s->prior_on && !s->hypo_on && !s->N.kn && !s->lang_on ? 1 : 0;
+    info->multi_step = mcmc_multi_step(s) ? 1 : 0;
     info->nphase = s->D.nphase;
     info->masked_s = s->masked_s;
     FsmLaunch L;

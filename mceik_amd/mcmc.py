@@ -545,14 +545,12 @@ class Sampler:
         self._last_full = True          # the last forward solved every model (init / restore)
         self._post = None               # (per_chain, nbins) while the streaming posterior is enabled
         self._temper = None             # (betas, swap_every) while parallel tempering is enabled
-        self._temper_base = None        # (attempts, accepts) of a restored checkpoint: added to the device counters
         self._block = None              # (rmin, rmax) while block proposals are enabled
-        self._block_base = None         # (attempts, accepts) of a restored checkpoint, as _temper_base
         self._prior = None              # (w_smooth, w_damp, vref digest) while the prior is enabled
         self._hypo = None               # (every, dmax, lo, hi) while hypocentre moves are enabled
-        self._hypo_base = None          # (attempts, accepts) of a restored checkpoint, as _temper_base
         self._nuis = None               # the options while the sampler holds nuisance state (nuis_enable .. nuis_clear)
-        self._nuis_base = None          # (attempts, accepts) of a restored checkpoint, as _temper_base
+        self._stats_base = {}           # "temper" / "block" / "hypo" / "nuis" -> (attempts, accepts) of a restored
+        #                                 checkpoint: added to the device counters (_move_stats)
         self._cov = None                # (probes [(kind, index)], within) while the sampler holds covariance sums
         self._lang = False              # Langevin moves were enabled at least once
         self._ess = None                # (nlevels, probes [(kind, index)]) while the sampler holds batch-means sums
@@ -722,14 +720,11 @@ class Sampler:
         if "posterior" in ck and self._post is not None:
             self._posterior_set(ck["posterior"])
         if tk is not None:
-            self.temper_stats(reset=True)
-            self._temper_base = (np.asarray(tk["attempts"], np.int64).copy(), np.asarray(tk["accepts"], np.int64).copy())
+            self._rebase_stats("temper", tk)
         if bk is not None:
-            self.block_stats(reset=True)
-            self._block_base = (np.asarray(bk["attempts"], np.int64).copy(), np.asarray(bk["accepts"], np.int64).copy())
+            self._rebase_stats("block", bk)
         if hk is not None:
-            self.hypo_stats(reset=True)
-            self._hypo_base = (np.asarray(hk["attempts"], np.int64).copy(), np.asarray(hk["accepts"], np.int64).copy())
+            self._rebase_stats("hypo", hk)
             sm = np.ascontiguousarray(hk["sum"], dtype=np.int64)
             sq = np.ascontiguousarray(hk["sq"], dtype=np.int64)
             assert sm.shape == (self.p.nevents, 3) and sq.shape == (self.p.nevents, 6)
@@ -738,13 +733,32 @@ class Sampler:
             if rc != 0:
                 raise RuntimeError(f"mceik_mcmc_hypo_moments_set failed ({rc})")
         if nk is not None:
-            self.nuis_stats(reset=True)
-            self._nuis_base = (np.asarray(nk["attempts"], np.int64).copy(), np.asarray(nk["accepts"], np.int64).copy())
+            self._rebase_stats("nuis", nk)
             self.nuis_moments_set(nk["moments"])
         if ck_cov is not None and self._cov is not None:
             self._cov_set(ck_cov)
         if ck_ess is not None and self._ess is not None:
             self._ess_set(ck_ess)
+
+    # --- attempt / accept counters of the moves (mceik_mcmc_{temper,block,hypo,nuis}_stats) ---
+    def _move_stats(self, name, n, reset, why=""):
+        """(attempts, accepts) int64 [n] of move `name`: the library's counters
+        plus those of a restored checkpoint (until a reset)."""
+        att, acc = np.zeros(n, np.int64), np.zeros(n, np.int64)
+        rc = getattr(self._L, f"mceik_mcmc_{name}_stats")(self._h, att.ctypes.data_as(C.c_void_p),
+                                                          acc.ctypes.data_as(C.c_void_p), int(reset))
+        if rc != 0:
+            raise RuntimeError(f"mceik_mcmc_{name}_stats failed ({rc}){why}")
+        if name in self._stats_base:
+            att, acc = att + self._stats_base[name][0], acc + self._stats_base[name][1]
+        if reset:
+            self._stats_base.pop(name, None)
+        return att, acc
+
+    def _rebase_stats(self, name, entry):
+        """restore(): zero the library's counters of move `name`; the checkpoint's ride on as the base."""
+        getattr(self, name + "_stats")(reset=True)
+        self._stats_base[name] = tuple(np.asarray(entry[k], np.int64).copy() for k in ("attempts", "accepts"))
 
     # --- streaming posterior (include/mceik.h mceik_mcmc_posterior_*) ---
     def posterior_enable(self, per_chain=True, nbins=64):
@@ -838,14 +852,14 @@ class Sampler:
                 f"mceik_mcmc_temper_enable failed ({rc}): nchains % ntemps == 0, betas[0] == 1, 0 < betas[r+1] <= "
                 "betas[r], swap_every >= 0, and no states in an enabled posterior")
         self._temper = (b.copy(), int(swap_every))
-        self._temper_base = None
+        self._stats_base.pop("temper", None)
 
     def temper_disable(self):
         rc = self._L.mceik_mcmc_temper_disable(self._h)
         if rc != 0:
             raise (ValueError if rc == 1 else RuntimeError)(f"mceik_mcmc_temper_disable failed ({rc})")
         self._temper = None
-        self._temper_base = None
+        self._stats_base.pop("temper", None)
 
     def _temper_on(self):
         if self._temper is None:
@@ -859,17 +873,7 @@ class Sampler:
 
     def temper_stats(self, reset=False):
         """(attempts, accepts) int64 [ntemps - 1]: swap rounds per rung pair (r, r + 1)."""
-        n = len(self._temper_on()[0]) - 1
-        att, acc = np.zeros(n, np.int64), np.zeros(n, np.int64)
-        rc = self._L.mceik_mcmc_temper_stats(self._h, att.ctypes.data_as(C.c_void_p), acc.ctypes.data_as(C.c_void_p),
-                                             int(reset))
-        if rc != 0:
-            raise RuntimeError(f"mceik_mcmc_temper_stats failed ({rc})")
-        if self._temper_base is not None:
-            att, acc = att + self._temper_base[0], acc + self._temper_base[1]
-        if reset:
-            self._temper_base = None
-        return att, acc
+        return self._move_stats("temper", len(self._temper_on()[0]) - 1, reset)
 
     def temper_swap(self, parity):
         """One swap round now (enqueued): rungs r, r + 1 with r % 2 == parity, drawn at the current step."""
@@ -892,29 +896,19 @@ class Sampler:
             raise (ValueError if rc == 1 else RuntimeError)(
                 f"mceik_mcmc_block_enable failed ({rc}): 0 <= rmin <= rmax <= 8")
         self._block = (int(rmin), int(rmax))
-        self._block_base = None
+        self._stats_base.pop("block", None)
 
     def block_disable(self):
         if self._L.mceik_mcmc_block_disable(self._h) != 0:
             raise RuntimeError("mceik_mcmc_block_disable failed")
         self._block = None
-        self._block_base = None
+        self._stats_base.pop("block", None)
 
     def block_stats(self, reset=False):
         """(attempts, accepts) int64 [rmax + 1]: proposals and accepted proposals by radius."""
         if self._block is None:
             raise RuntimeError("block proposals are not enabled (Sampler.block_enable)")
-        n = self._block[1] + 1
-        att, acc = np.zeros(n, np.int64), np.zeros(n, np.int64)
-        rc = self._L.mceik_mcmc_block_stats(self._h, att.ctypes.data_as(C.c_void_p), acc.ctypes.data_as(C.c_void_p),
-                                            int(reset))
-        if rc != 0:
-            raise RuntimeError(f"mceik_mcmc_block_stats failed ({rc})")
-        if self._block_base is not None:
-            att, acc = att + self._block_base[0], acc + self._block_base[1]
-        if reset:
-            self._block_base = None
-        return att, acc
+        return self._move_stats("block", self._block[1] + 1, reset)
 
     # --- discrete Langevin moves (include/mceik.h mceik_mcmc_lang_*) ---
     def lang_enable(self, every, offset=0, sigma=8.0, dmax=16, mem_bytes=None):
@@ -1065,14 +1059,14 @@ class Sampler:
                 f"mceik_mcmc_hypo_enable failed ({rc}): every >= 0, dmax >= 0, a box lo <= hi inside the grid that holds "
                 "every chain's positions, tt_interp = 0, and no states in an enabled posterior")
         self._hypo = (int(every), dm, lo, hi)
-        self._hypo_base = None
+        self._stats_base.pop("hypo", None)
 
     def hypo_disable(self):
         """Later steps are velocity steps again; the positions stay where they are, per chain."""
         if self._L.mceik_mcmc_hypo_disable(self._h) != 0:
             raise RuntimeError("mceik_mcmc_hypo_disable failed")
         self._hypo = None
-        self._hypo_base = None
+        self._stats_base.pop("hypo", None)
 
     def hypo_positions(self):
         """int32 [nchains, nev, 3]: every chain's node (ix, iy, iz) per event (after a first `hypo_enable`)."""
@@ -1096,17 +1090,7 @@ class Sampler:
 
     def hypo_stats(self, reset=False):
         """(attempts, accepts) int64 [nev]: moves tried and accepted per event, over the chains."""
-        n = self.p.nevents
-        att, acc = np.zeros(n, np.int64), np.zeros(n, np.int64)
-        rc = self._L.mceik_mcmc_hypo_stats(self._h, att.ctypes.data_as(C.c_void_p), acc.ctypes.data_as(C.c_void_p),
-                                           int(reset))
-        if rc != 0:
-            raise RuntimeError(f"mceik_mcmc_hypo_stats failed ({rc})")
-        if self._hypo_base is not None:
-            att, acc = att + self._hypo_base[0], acc + self._hypo_base[1]
-        if reset:
-            self._hypo_base = None
-        return att, acc
+        return self._move_stats("hypo", self.p.nevents, reset)
 
     def hypo_last(self):
         """The last hypocentre step: (cand int32 [nchains, nev, 3] = current + d,
@@ -1201,7 +1185,7 @@ class Sampler:
                       "dt": float(statics_dt) if statics_dt is not None else None,
                       "lam": None if lam is None else lam.copy(), "lnlam": None if lnlam is None else lnlam.copy(),
                       "norm": None if norm is None else nm.copy()}
-        self._nuis_base = None
+        self._stats_base.pop("nuis", None)
         self._last_full = True
 
     def nuis_disable(self):
@@ -1219,7 +1203,7 @@ class Sampler:
         if rc != 0:
             raise (ValueError if rc == 1 else RuntimeError)(f"mceik_mcmc_nuis_clear failed ({rc})")
         self._nuis = None
-        self._nuis_base = None
+        self._stats_base.pop("nuis", None)
         self._last_full = True
 
     def _nuis_held(self, rc, what):
@@ -1263,15 +1247,8 @@ class Sampler:
         """(attempts, accepts) int64 [nphase + nphase * nstat] over the chains:
         entry ph the noise index of phase ph, entry nphase + ph * nstat + k the
         static of station k (a pair counts on both its stations)."""
-        n = self.p.nphase * (1 + self.p.nstat)
-        att, acc = np.zeros(n, np.int64), np.zeros(n, np.int64)
-        self._nuis_held(self._L.mceik_mcmc_nuis_stats(self._h, att.ctypes.data_as(C.c_void_p),
-                                                      acc.ctypes.data_as(C.c_void_p), int(reset)), "mceik_mcmc_nuis_stats")
-        if self._nuis_base is not None:
-            att, acc = att + self._nuis_base[0], acc + self._nuis_base[1]
-        if reset:
-            self._nuis_base = None
-        return att, acc
+        return self._move_stats("nuis", self.p.nphase * (1 + self.p.nstat), reset,
+                                ": the sampler holds no noise / statics values (nuis_enable)")
 
     def nuis_last(self):
         """The last nuisance step, per chain and sub-move: (rec int32 [nchains,
@@ -1665,23 +1642,31 @@ class PosteriorSummary:
         return np.where(total > 0, out, np.nan)
 
 
+def _gather_merged(parts, group, dst):
+    """This rank's exact partials (anything with merge()) gathered over the
+    torch.distributed `group` as host objects and merged on rank `dst`: the
+    merged partials there, None on the other ranks; without a group, `parts`."""
+    if group is None:
+        return parts
+    import torch.distributed as dist
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    every = [None] * world if rank == dst else None
+    dist.gather_object(parts, every, dst=dst, group=group)
+    if rank != dst:
+        return None
+    parts = every[0]
+    for other in every[1:]:
+        parts.merge(other)
+    return parts
+
+
 def posterior_summary(smp: Sampler, group=None, dst=0):
     """`PosteriorSummary` of a sampler's streaming posterior.  With a
     torch.distributed `group` (one process per GPU, each with its chain shard)
     the ranks' exact partials are gathered as host objects and merged on rank
     `dst`, which gets the summary of all chains; the other ranks get None."""
-    parts = smp.posterior_partials()
-    if group is not None:
-        import torch.distributed as dist
-        rank, world = dist.get_rank(group), dist.get_world_size(group)
-        every = [None] * world if rank == dst else None
-        dist.gather_object(parts, every, dst=dst, group=group)
-        if rank != dst:
-            return None
-        parts = every[0]
-        for other in every[1:]:
-            parts.merge(other)
-    return PosteriorSummary(parts)
+    parts = _gather_merged(smp.posterior_partials(), group, dst)
+    return None if parts is None else PosteriorSummary(parts)
 
 
 class CovPartials:
@@ -1763,18 +1748,8 @@ def cov_summary(smp: Sampler, group=None, dst=0):
     `group` the ranks' exact partials are gathered as host objects and merged
     on rank `dst`, which gets the summary of all chains; the other ranks get
     None (as `posterior_summary`)."""
-    parts = smp.cov_partials()
-    if group is not None:
-        import torch.distributed as dist
-        rank, world = dist.get_rank(group), dist.get_world_size(group)
-        every = [None] * world if rank == dst else None
-        dist.gather_object(parts, every, dst=dst, group=group)
-        if rank != dst:
-            return None
-        parts = every[0]
-        for other in every[1:]:
-            parts.merge(other)
-    return CovSummary(parts)
+    parts = _gather_merged(smp.cov_partials(), group, dst)
+    return None if parts is None else CovSummary(parts)
 
 
 def ess_check(nlevels, xmax):
@@ -1867,18 +1842,8 @@ def ess_summary(smp: Sampler, group=None, level=None, dst=0):
     torch.distributed `group` the ranks' exact partials are gathered as host
     objects and merged on rank `dst`, which gets the summary of all chains;
     the other ranks get None (as `posterior_summary`)."""
-    parts = smp.ess_partials()
-    if group is not None:
-        import torch.distributed as dist
-        rank, world = dist.get_rank(group), dist.get_world_size(group)
-        every = [None] * world if rank == dst else None
-        dist.gather_object(parts, every, dst=dst, group=group)
-        if rank != dst:
-            return None
-        parts = every[0]
-        for other in every[1:]:
-            parts.merge(other)
-    return EssSummary(parts, level)
+    parts = _gather_merged(smp.ess_partials(), group, dst)
+    return None if parts is None else EssSummary(parts, level)
 
 
 def picks_from_forward(device=0, precision=64):
