@@ -765,6 +765,124 @@ int mceik_ess_lstar(int nlevels, long long n);
 int mceik_ess_merge(mceik_ess_partials *dst, const mceik_ess_partials *src);
 int mceik_ess_finish(const mceik_ess_partials *p, int level, double *tau, double *ess, double *mcse, int *level_used);
 
+/* ---- pick residuals, origin times and data-fit checks (csrc/fit.hip)
+ * The data side of a run, streamed: per pick the mean and spread of its
+ * residual and of its standardised residual, per event the origin time and a
+ * reduced misfit, per (phase, station) the mean residual and a histogram of
+ * the standardised residuals.  Kept states are never stored and no forward
+ * solve is repeated.  Off by default; with it off nothing changes.
+ *
+ * Per kept step and cold chain, from the chain's current state exactly as its
+ * logL sees it (the chain's effective var / tcorr while nuisance state is
+ * held, its own event nodes, trilinear tables under tt_interp): for every
+ * event e the objective's arithmetic in fp64 over the event's
+ * used picks j in CSR order, every table value te_j from the chain's current
+ * tables,
+ *   xnorm = sum_j 1 / var_j                        (from 0.0, in order)
+ *   t0    = sum_j ((1 / var_j) / xnorm) (tc_j - te_j),   tc_j = tobs_j - tcorr_j
+ *   r_j   = tc_j - (te_j + t0),   z_j = (1.0 / var_j) * r_j      (objfn = sum z^2 / 2)
+ * and the integers, rint = fp64 round-half-even, sat32 = clamp to +-(2^31 - 1):
+ *   q_j  = sat32(rint(r_j * (1 / tick)))           tick: a power of two (seconds), so the scaling is exact
+ *   zq_j = sat32(rint(z_j * 1024.0))
+ *   tq_e = sat32(rint((t0 - t0_ref[e]) * (1 / tick)))     (0 for an event without a used pick)
+ *   b_j  = clamp(floor(z_j * (nbins / (2 zmax)) + nbins / 2), 0, nbins - 1)   in that order, in fp64
+ * Every clamp of q, zq, tq bumps sat[0], sat[1], sat[2] (a NaN clamps to the
+ * upper bound).  Masked picks contribute nothing.  The sums, pooled over the
+ * cold chains and the kept steps:
+ *   sq, szq [nobs]  int64      sums of q, zq (two's complement)
+ *   sq2, szq2 [nobs][2]        sums of q^2, zq^2: 128 bits as unsigned (lo, hi) words
+ *   stq [nev] int64, stq2 [nev][2]                 the same of tq
+ *   hist [nphase][nstat][nbins] int64              counts of b_j by the pick's phase and station
+ * Every update is an integer addition: the words do not depend on the order of
+ * chains, pipes, launches, shards or ranks, and partials merge by addition.
+ * |q| < 2^31, so an int64 sum holds 2^32 states (chains x kept steps) and a
+ * 128-bit sum of squares never wraps before it.  Memory: 4 (3 nobs + nev)
+ * bytes per chain (the last kept step's words, mceik_mcmc_fit_last) plus 48
+ * nobs + 24 nev + 8 nphase nstat nbins pooled.
+ *
+ * While enabled, mceik_mcmc_run adds the cold chains' state after every kept
+ * step by two kernels queued behind the step: no host synchronisation, and
+ * the chains are bit for bit those of a run without it.  With multi-step
+ * launches a launch ends right after the next kept step, as for the streaming
+ * posterior.  A one-model sampler holds its current tables while enabled, as
+ * it does while nuisance state is held (enable runs one forward to fill them
+ * when they were not held), and steps with one launch per step
+ * (mceik_mcmc_info.multi_step reports 0 until disable): the per-step accept
+ * keeps the tables current, the multi-step kernel only does for two models.
+ *
+ * enable returns 1 for a tick that is not 2^k (k in [-64, 64]), nbins odd or
+ * outside [2, 256], zmax not positive and finite, a t0_ref that is not finite,
+ * and while the accumulators hold states of other options; with the options
+ * of the held sums it resumes them.  t0_ref NULL: zeros.  disable stops
+ * accumulating and keeps the sums; clear drops them.
+ * Every function returns 0, 1 on invalid arguments or -1 on a device failure
+ * (enable: 2 when the forward that fills the tables fails). */
+#define MCEIK_FIT_MAX_BINS 256
+typedef struct mceik_fit_opts {
+    double tick;                               /* seconds per unit of q and tq: 2^k */
+    int nbins;                                 /* even, 2 .. MCEIK_FIT_MAX_BINS */
+    double zmax;                               /* the histogram covers [-zmax, zmax]; the edge bins take the tails */
+    const double *t0_ref;                      /* [nev] subtracted from t0 before scaling, or NULL */
+} mceik_fit_opts;
+typedef struct mceik_fit_partials {            /* caller-allocated host arrays */
+    int nobs, nev, nphase, nstat, nbins;
+    double tick, zmax;
+    long long nchains, nkept;                  /* chains summed, states per chain */
+    int *obs_ptr;                              /* [nev + 1] the catalogue's CSR rows */
+    int *obs_stat, *obs_phase, *obs_mask;      /* [nobs] station, phase (0 P, 1 S), 1 = not fit */
+    double *t0_ref;                            /* [nev] */
+    long long *sq, *szq;                       /* [nobs] */
+    unsigned long long *sq2, *szq2;            /* [nobs][2] = lo, hi words */
+    long long *stq;                            /* [nev] */
+    unsigned long long *stq2;                  /* [nev][2] */
+    long long *hist;                           /* [nphase][nstat][nbins] */
+    long long sat[3];                          /* clamped q, zq, tq */
+} mceik_fit_partials;
+int mceik_mcmc_fit_enable(mceik_mcmc *s, const mceik_fit_opts *o);
+int mceik_mcmc_fit_disable(mceik_mcmc *s);
+int mceik_mcmc_fit_clear(mceik_mcmc *s);
+/* Adds the cold chains' current state now (enqueued on the sampler's stream). */
+int mceik_mcmc_fit_accumulate(mceik_mcmc *s);
+/* Host copies of / replacements for the accumulators (checkpoints): n states
+ * per chain and the arrays above (sat [3]).  get synchronises, any pointer may
+ * be NULL; set needs every array. */
+int mceik_mcmc_fit_get(mceik_mcmc *s, long long *n, long long *sq, long long *szq, unsigned long long *sq2,
+                       unsigned long long *szq2, long long *stq, unsigned long long *stq2, long long *hist,
+                       long long *sat);
+int mceik_mcmc_fit_set(mceik_mcmc *s, long long n, const long long *sq, const long long *szq,
+                       const unsigned long long *sq2, const unsigned long long *szq2, const long long *stq,
+                       const unsigned long long *stq2, const long long *hist, const long long *sat);
+/* The pooled words as partials.  Fills every scalar of *out and the arrays it
+ * points to.  Synchronises. */
+int mceik_mcmc_fit_partials(mceik_mcmc *s, mceik_fit_partials *out);
+/* The last kept step's words of every chain of the sampler (rows of chains
+ * that are not cold stay 0): q, zq [nchains][nobs] (0 for a masked pick), tq
+ * [nchains][nev]; any may be NULL.  Synchronises. */
+int mceik_mcmc_fit_last(mceik_mcmc *s, int *q, int *zq, int *tq);
+/* Host only (no GPU call).
+ * check: 0 when tick is 2^k, k in [-64, 64], and a residual of rmax >= 0
+ * seconds does not saturate (rint(rmax / tick) <= 2^31 - 1), else 1.
+ * merge: dst += src, every word with its carry; 1 unless the shapes, tick,
+ * zmax, t0_ref, the observations' rows and nkept agree.
+ * finish: with N = nchains nkept, every exact sum (for a standard deviation
+ * the exact integer N Q - S^2) is converted to double once, then only *, / and
+ * sqrt:
+ *   pick_mean = sq tick / N            pick_sd = sqrt((N sq2 - sq^2) / (N (N - 1))) tick      [nobs]
+ *   pick_zmean = szq / 1024 / N        pick_zrms = sqrt(szq2 / (1024^2 N))                    [nobs]
+ *   t0_mean, t0_sd: the same of stq, stq2, the mean plus t0_ref                              [nev]
+ *   ev_misfit = (sum over the event's used picks of szq2) / (1024^2 N (used picks - 1))      [nev]
+ *   sta_mean = (sum over the row's used picks of sq) tick / (N picks): the data's estimate
+ *   of a station static; sta_zrms = sqrt(sum of szq2 / (1024^2 N picks))         [nphase][nstat]
+ *   phase_zrms: the same over every used pick of the phase                                [nphase]
+ * NaN: everything when nkept < 2 or nchains < 1; a masked pick; an event or a
+ * row without a used pick (ev_misfit: with fewer than two).  Any output may be
+ * NULL. */
+int mceik_fit_check(double tick, double rmax);
+int mceik_fit_merge(mceik_fit_partials *dst, const mceik_fit_partials *src);
+int mceik_fit_finish(const mceik_fit_partials *p, double *pick_mean, double *pick_sd, double *pick_zmean,
+                     double *pick_zrms, double *t0_mean, double *t0_sd, double *ev_misfit, double *sta_mean,
+                     double *sta_zrms, double *phase_zrms);
+
 /* ---- multi-rank runs (one process per GPU; csrc/comm.hip) ---------------
  * The sampler's only collective is the checkpoint gather (SURVEY s.8e) over
  * RCCL (xGMI on one node).  Bootstrap as RCCL's: rank 0 calls

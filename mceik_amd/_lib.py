@@ -174,6 +174,26 @@ class EssPartials(C.Structure):
                 ("A", C.c_void_p), ("Q", C.c_void_p), ("P", C.c_void_p)]
 
 
+FIT_MAX_BINS = 256
+
+
+class FitOpts(C.Structure):
+    """mceik_fit_opts (include/mceik.h)."""
+    _fields_ = [("tick", C.c_double), ("nbins", C.c_int), ("zmax", C.c_double), ("t0_ref", C.c_void_p)]
+
+
+class FitPartials(C.Structure):
+    """mceik_fit_partials (include/mceik.h): caller-allocated host arrays."""
+    _fields_ = [("nobs", C.c_int), ("nev", C.c_int), ("nphase", C.c_int), ("nstat", C.c_int), ("nbins", C.c_int),
+                ("tick", C.c_double), ("zmax", C.c_double),
+                ("nchains", C.c_longlong), ("nkept", C.c_longlong),
+                ("obs_ptr", C.c_void_p), ("obs_stat", C.c_void_p), ("obs_phase", C.c_void_p), ("obs_mask", C.c_void_p),
+                ("t0_ref", C.c_void_p),
+                ("sq", C.c_void_p), ("szq", C.c_void_p), ("sq2", C.c_void_p), ("szq2", C.c_void_p),
+                ("stq", C.c_void_p), ("stq2", C.c_void_p), ("hist", C.c_void_p),
+                ("sat", C.c_longlong * 3)]
+
+
 # every extern "C" symbol include/*.h declares
 EXPORTS = ("eikonal3d_serial_driver", "eikonal3d_serial_driver_sp", "eikonal3d_batch_solve", "eikonal3d_initialize", "eikonal3d_solve",
            "eikonal3d_finalize", "locate3d_gridsearch__double64", "locate3d_gridsearch__float64",
@@ -208,6 +228,9 @@ EXPORTS = ("eikonal3d_serial_driver", "eikonal3d_serial_driver_sp", "eikonal3d_b
            "mceik_mcmc_ess_enable", "mceik_mcmc_ess_disable", "mceik_mcmc_ess_clear", "mceik_mcmc_ess_accumulate",
            "mceik_mcmc_ess_get", "mceik_mcmc_ess_set", "mceik_mcmc_ess_partials", "mceik_ess_check", "mceik_ess_lstar",
            "mceik_ess_merge", "mceik_ess_finish",
+           "mceik_mcmc_fit_enable", "mceik_mcmc_fit_disable", "mceik_mcmc_fit_clear", "mceik_mcmc_fit_accumulate",
+           "mceik_mcmc_fit_get", "mceik_mcmc_fit_set", "mceik_mcmc_fit_partials", "mceik_mcmc_fit_last",
+           "mceik_fit_check", "mceik_fit_merge", "mceik_fit_finish",
            "mceik_mcmc_lang_enable", "mceik_mcmc_lang_disable", "mceik_mcmc_lang_get", "mceik_mcmc_lang_stats",
            "mceik_mcmc_lang_last", "mceik_det_exp", "mceik_lang_cell",
            "mceik_parms_defaults", "mceik_parms_set", "mceik_parms_read", "mceik_parms_args", "mceik_parms_write",
@@ -448,5 +471,24 @@ def lib():
     L.mceik_ess_merge.argtypes = [C.POINTER(EssPartials), C.POINTER(EssPartials)]
     L.mceik_ess_finish.restype = C.c_int
     L.mceik_ess_finish.argtypes = [C.POINTER(EssPartials), C.c_int] + [C.c_void_p] * 3 + [pi]
+    L.mceik_mcmc_fit_enable.restype = C.c_int
+    L.mceik_mcmc_fit_enable.argtypes = [C.c_void_p, C.POINTER(FitOpts)]
+    for name in ("mceik_mcmc_fit_disable", "mceik_mcmc_fit_clear", "mceik_mcmc_fit_accumulate"):
+        getattr(L, name).restype = C.c_int
+        getattr(L, name).argtypes = [C.c_void_p]
+    L.mceik_mcmc_fit_get.restype = C.c_int
+    L.mceik_mcmc_fit_get.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)] + [C.c_void_p] * 8
+    L.mceik_mcmc_fit_set.restype = C.c_int
+    L.mceik_mcmc_fit_set.argtypes = [C.c_void_p, C.c_longlong] + [C.c_void_p] * 8
+    L.mceik_mcmc_fit_partials.restype = C.c_int
+    L.mceik_mcmc_fit_partials.argtypes = [C.c_void_p, C.POINTER(FitPartials)]
+    L.mceik_mcmc_fit_last.restype = C.c_int
+    L.mceik_mcmc_fit_last.argtypes = [C.c_void_p] * 4
+    L.mceik_fit_check.restype = C.c_int
+    L.mceik_fit_check.argtypes = [C.c_double, C.c_double]
+    L.mceik_fit_merge.restype = C.c_int
+    L.mceik_fit_merge.argtypes = [C.POINTER(FitPartials), C.POINTER(FitPartials)]
+    L.mceik_fit_finish.restype = C.c_int
+    L.mceik_fit_finish.argtypes = [C.POINTER(FitPartials)] + [C.c_void_p] * 10
     _lib = L
     return L

@@ -11,6 +11,7 @@
 #include "block.h"
 #include "cov.h"
 #include "ess.h"
+#include "fit.h"
 #include "fsm_common.h"
 #include "hypo.h"
 #include "lang.h"
@@ -25,8 +26,8 @@
 // A pipe: a part of the chains stepped on a stream of its own.  D, B, P, H, N, L, fb
 // and fb_hyp are views of the sampler's restricted to the pipe's chains;
 // pipes_refresh alone writes them.  (The accumulators of kept states --
-// posterior, covariances, batch means -- have no views: their accumulate calls
-// take the pipe's chain offset.)
+// posterior, covariances, batch means, data fit -- have no views: their
+// accumulate calls take the pipe's chain offset.)
 struct Pipe {
     McmcDev D;
     BlockDev B;
@@ -129,7 +130,7 @@ struct mceik_mcmc {
     NuisDev N;
     NuisDev Nbuf;                      // the arrays of the first enable, kept across clear
     int nuis_cap_sub, nuis_cap_nk;     // sub-moves / ladder entries the arrays hold
-    float *ttab_cur1;                  // one model: [nchains][nstat][nev] current tables while N.kn is set
+    float *ttab_cur1;                  // one model: [nchains][nstat][nev] current tables while N.kn is set or fit_on
     long long nuis_n;                  // states in the moments (cold chains x kept steps)
     std::vector<int> h_ostat, h_omask, h_ophase;   // [nobs] the observations' station, mask and phase (host copies)
     // Probe-to-cell covariances (cov.hip); off by default.  cov is
@@ -144,6 +145,14 @@ struct mceik_mcmc {
     // launch ends right after the next kept step, as it does for the posterior.
     McmcEss *ess;
     bool ess_on;
+    // Pick residuals, origin times and data-fit checks (fit.hip);
+    // off by default.  fit is null until an enable and again after a clear;
+    // fit_on: kept steps add to it (a disable keeps the sums).  While on, a
+    // multi-step launch ends right after the next kept step, and a one-model
+    // sampler holds its current tables (D.ttab_cur = ttab_cur1, as with nuisance
+    // state) and takes the per-step branch, whose accept copies them.
+    McmcFit *fit;
+    bool fit_on;
     // Discrete Langevin moves (lang.hip); off by default.  L's
     // arrays are null until the first enable, which allocates everything a step
     // uses: the per-chain arrays, and per pipe (lang_pipe) the fields, the
@@ -193,11 +202,21 @@ int temper_round(mceik_mcmc *s, int parity);
 // fold sits between a step's proposal and its forward); hypocentre moves (a
 // hypocentre step has kernels and a batch of its own); held nuisance state (it
 // enters every logL, which the multi-step kernel's epilogue does not know);
-// Langevin moves (a Langevin step is a pipeline of launches of its own).
+// Langevin moves (a Langevin step is a pipeline of launches of its own); the
+// data-fit sums of a one-model sampler (they read the chains' current tables,
+// which the multi-step kernel's epilogue keeps for two models only).
 static inline bool mcmc_multi_step(const mceik_mcmc *s)
 {
-    return s->persist && !s->block_on && !s->prior_on && !s->hypo_on && !s->N.kn && !s->lang_on;
+    return s->persist && !s->block_on && !s->prior_on && !s->hypo_on && !s->N.kn && !s->lang_on &&
+           !(s->fit_on && s->D.nphase == 1);
 }
+// A one-model sampler's current tables (sampler_api.hip).  hold: while nuisance
+// state is held or the data-fit sums are on, D.ttab_cur = ttab_cur1 (allocated
+// on first need); when they were not held yet, one full forward fills them
+// (logL is recomputed from them: the same value).  drop: once neither needs
+// them, the sampler is the plain one again.  Both synchronise; two models: no-ops.
+int mcmc_tables1_hold(mceik_mcmc *s, const char *who);
+int mcmc_tables1_drop(mceik_mcmc *s);
 // Bytes pipe k's Langevin step needs for chunks of m chains: the fields (u), the
 // workspaces of the forward with fields (fws) and of the adjoint (aws), the
 // pick weights (evw) and the adjoint's per-solve rows (gs), each a multiple of

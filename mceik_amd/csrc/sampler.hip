@@ -4,7 +4,8 @@
 //
 // Host orchestration only.  The numerics live in fsm_kernel.hip,
 // fsm16_kernel.hip, mcmc_kernels.hip, temper.hip, block.hip, prior.hip,
-// hypo.hip, nuis.hip, lang.hip, adjoint.hip, posterior.hip, cov.hip and ess.hip.
+// hypo.hip, nuis.hip, lang.hip, adjoint.hip, posterior.hip, cov.hip, ess.hip
+// and fit.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -723,8 +724,9 @@ static StepPlan plan_step(const mceik_mcmc *s, long long gs)
     return q;
 }
 
-// The kept-state hook.  Five consumers see the cold chains of a kept step:
-// posterior, hypocentre moments, nuisance moments, covariances, batch means.
+// The kept-state hook.  Six consumers see the cold chains of a kept step:
+// posterior, hypocentre moments, nuisance moments, covariances, batch means,
+// data fit.
 // kept_queue queues those that are on for the cold chains of pipe p's view on
 // stream st; kept_counted counts the state on the host once every pipe is
 // queued (mcmc_ess_k depends on that count alone, so every pipe reads the
@@ -739,6 +741,7 @@ static int kept_queue(mceik_mcmc *s, const Pipe &p, hipStream_t st)
     if (s->nuis_on && s->N.kn) HIPCHK(nuis_moments(p.D, p.N, n, st));
     if (s->cov_on) HIPCHK(mcmc_cov_accumulate(s->cov, p.D, p.H, p.N, off, n, st));
     if (s->ess_on) HIPCHK(mcmc_ess_accumulate(s->ess, p.D, p.H, p.N, off, n, mcmc_ess_k(s->ess), st));
+    if (s->fit_on) HIPCHK(mcmc_fit_accumulate(s->fit, p.D, p.H, p.N, off, n, st));
     return 0;
 }
 
@@ -749,6 +752,7 @@ static void kept_counted(mceik_mcmc *s)
     if (s->nuis_on && s->N.kn) s->nuis_n += temper_cold(s);
     if (s->cov_on) mcmc_cov_counted(s->cov);
     if (s->ess_on) mcmc_ess_counted(s->ess);
+    if (s->fit_on) mcmc_fit_counted(s->fit);
 }
 
 // Chains [off, off + m) of pipe p's step batch as a Langevin step runs them:
@@ -848,9 +852,9 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
         // FSM launch (the kernel accepts, keeps and proposes the rest)
         for (int done = 0; done < nsteps;) {
             int n = std::min(nsteps - done, MCEIK_MC_CHUNK);
-            // posterior, covariances or batch means on: the launch ends right after the next
-            // kept step, when every chain's current state is its state after that step
-            if (s->post || s->cov_on || s->ess_on) n = (int)std::min<long long>(n, next_kept_step(s) - s->step + 1);
+            // posterior, covariances, batch means or data fit on: the launch ends right after the
+            // next kept step, when every chain's current state is its state after that step
+            if (s->post || s->cov_on || s->ess_on || s->fit_on) n = (int)std::min<long long>(n, next_kept_step(s) - s->step + 1);
             // tempering: this step's swap round first; the launch ends before the next one
             const StepPlan q = plan_step(s, s->step);         // (a velocity step: mcmc_multi_step)
             if (q.swap && temper_round(s, q.parity)) return -1;
@@ -974,6 +978,7 @@ extern "C" int mceik_mcmc_finalize(mceik_mcmc **ps)
     mcmc_post_free(s->post);
     mcmc_cov_free(s->cov);
     mcmc_ess_free(s->ess);
+    mcmc_fit_free(s->fit);
     for (int i = 0; i < 2 * s->ev_made; i++) hipEventDestroy(s->ev[i]);
     if (s->ws) hipFree(s->ws);
     delete s;

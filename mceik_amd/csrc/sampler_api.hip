@@ -50,6 +50,29 @@ static int forward_logl(mceik_mcmc *s, const char *who)
     return check_forward_ierr(s, who) ? 2 : 0;
 }
 
+// A one-model sampler's current tables (sampler.h).
+int mcmc_tables1_hold(mceik_mcmc *s, const char *who)
+{
+    if (s->D.nphase != 1 || s->D.ttab_cur) return 0;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    if (!s->ttab_cur1 && dalloc(s, &s->ttab_cur1, (size_t)s->D.nchains * s->D.nstat * s->D.nev)) return -1;
+    s->D.ttab_cur = s->ttab_cur1;
+    s->fb_all.ttab = s->ttab_cur1;
+    if (pipes_refresh(s)) return -1;
+    return forward_logl(s, who);
+}
+
+int mcmc_tables1_drop(mceik_mcmc *s)
+{
+    if (s->D.nphase != 1 || !s->D.ttab_cur || s->N.kn || s->fit_on) return 0;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    s->D.ttab_cur = nullptr;
+    s->fb_all.ttab = s->fb.ttab;
+    return pipes_refresh(s);
+}
+
 // ---------------------------------------------------------------------------
 // parallel tempering (include/mceik.h mceik_mcmc_temper_*)
 
@@ -614,10 +637,10 @@ extern "C" int mceik_mcmc_nuis_enable(mceik_mcmc *s, const mceik_nuis_opts *o)
         memset(&A, 0, sizeof(A));
         unsigned long long *cnt = nullptr;
         int *dact = nullptr;
-        float *tc1 = nullptr;
+        float *tc1 = s->ttab_cur1;     // (shared with the data-fit sums: whichever needed them first made them)
         if (dalloc(s, &A.kn, nn) || dalloc(s, &A.kc, nc) || dalloc(s, &A.var_eff, (size_t)nch * nobs) ||
             dalloc(s, &A.tcorr_eff, (size_t)nch * nobs) || dalloc(s, &cnt, 2 * nuis_npar(D)) || dalloc(s, &dact, (size_t)nph * nst) ||
-            (nph == 1 && dalloc(s, &tc1, (size_t)nch * nst * D.nev)))
+            (nph == 1 && !tc1 && dalloc(s, &tc1, (size_t)nch * nst * D.nev)))
             return -1;
         A.attempts = cnt;
         A.accepts = cnt + nuis_npar(D);
@@ -696,7 +719,7 @@ extern "C" int mceik_mcmc_nuis_clear(mceik_mcmc *s)
     HIPCHK(hipStreamSynchronize(s->stream));
     s->nuis_on = false;
     memset(&s->N, 0, sizeof(s->N));
-    if (s->D.nphase == 1) {
+    if (s->D.nphase == 1 && !s->fit_on) {       // (the data-fit sums keep reading the current tables)
         s->D.ttab_cur = nullptr;
         s->fb_all.ttab = s->fb.ttab;
     }

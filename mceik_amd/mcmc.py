@@ -554,6 +554,8 @@ class Sampler:
         self._cov = None                # (probes [(kind, index)], within) while the sampler holds covariance sums
         self._lang = False              # Langevin moves were enabled at least once
         self._ess = None                # (nlevels, probes [(kind, index)]) while the sampler holds batch-means sums
+        self._fit = None                # (tick, nbins, zmax, t0_ref) while the sampler holds data-fit sums
+        self._fit_active = False        # ... and adds kept steps to them (fit_enable .. fit_disable)
 
     @property
     def model_shape(self):
@@ -666,6 +668,8 @@ class Sampler:
             ck["cov"] = self.cov_raw()
         if self._ess is not None:        # likewise: the open batches are part of a run that summarises itself
             ck["ess"] = self.ess_raw()
+        if self._fit is not None:        # likewise
+            ck["fit"] = self.fit_raw()
         return ck
 
     def restore(self, ck, recompute_logl=False):
@@ -698,6 +702,8 @@ class Sampler:
             recompute_logl = True
         elif self._nuis is not None:
             recompute_logl = True
+        if self._fit_active and self.p.nphase == 1:
+            recompute_logl = True        # a one-model sampler holds current tables for the data-fit sums: the forward makes them
         ck_cov = ck.get("cov")           # a sampler without the sums ignores the entry; one with them wants its list
         if ck_cov is not None and self._cov is not None and \
                 ([tuple(int(x) for x in pr) for pr in ck_cov["probes"]], bool(ck_cov["within"])) != self._cov:
@@ -706,6 +712,11 @@ class Sampler:
         if ck_ess is not None and self._ess is not None and \
                 (int(ck_ess["nlevels"]), [tuple(int(x) for x in pr) for pr in ck_ess["probes"]]) != self._ess:
             raise ValueError("the checkpoint's batch-means sums were accumulated with another nlevels or probe list")
+        ck_fit = ck.get("fit")           # likewise
+        if ck_fit is not None and self._fit is not None and \
+                ((float(ck_fit["tick"]), int(ck_fit["nbins"]), float(ck_fit["zmax"])) != self._fit[:3] or
+                 np.asarray(ck_fit["t0_ref"], np.float64).tobytes() != self._fit[3].tobytes()):
+            raise ValueError("the checkpoint's data-fit sums were accumulated with other options")
         v = np.ascontiguousarray(ck["v"], dtype=np.int32)
         assert v.shape == self.model_shape
         logl = None if recompute_logl else np.ascontiguousarray(ck["logl"], dtype=np.float64)
@@ -739,6 +750,8 @@ class Sampler:
             self._cov_set(ck_cov)
         if ck_ess is not None and self._ess is not None:
             self._ess_set(ck_ess)
+        if ck_fit is not None and self._fit is not None:
+            self._fit_set(ck_fit)
 
     # --- attempt / accept counters of the moves (mceik_mcmc_{temper,block,hypo,nuis}_stats) ---
     def _move_stats(self, name, n, reset, why=""):
@@ -1508,6 +1521,118 @@ class Sampler:
         out.nchains, out.nkept = int(st.nchains), int(st.nkept)
         return out
 
+    # --- pick residuals, origin times and data-fit checks (include/mceik.h mceik_mcmc_fit_*) ---
+    def fit_enable(self, tick=2.0 ** -20, nbins=64, zmax=8.0, t0_ref=None):
+        """Stream the data side of run() over the cold chains' kept states
+        (DESIGN.md s.20): `fit_summary` then gives per pick the mean and spread
+        of its residual and of its standardised residual z, per event the
+        origin time and a reduced misfit, per (phase, station) the mean
+        residual, the rms of z and a histogram of z with `nbins` (even, 2 ..
+        256) bins over [-`zmax`, `zmax`].  Residuals and origin times are
+        summed in units of `tick` seconds (a power of two; |value| / tick <
+        2^31, see `fit_check`); `t0_ref` [nev] (None: zeros) is subtracted
+        from the origin times first, so absolute-epoch catalogues stay in
+        range.  Everything is taken from the chain's current tables and
+        effective observations, exactly as its logL sees them.  The chains do
+        not change.  A one-model sampler holds its current tables while this is
+        on and steps with one launch per step (`info()["multi_step"]` is False
+        until `fit_disable`).  Enabling again with the options of held sums
+        resumes them (`fit_disable` keeps them, `fit_clear` drops them); other
+        options are refused while they hold states."""
+        nev = self.p.nevents
+        ref = np.zeros(nev) if t0_ref is None else np.ascontiguousarray(t0_ref, dtype=np.float64).ravel()
+        if ref.size != nev:
+            raise ValueError("fit_enable: t0_ref is one time per event")
+        o = _lib.FitOpts()
+        o.tick, o.nbins, o.zmax, o.t0_ref = float(tick), int(nbins), float(zmax), ref.ctypes.data
+        rc = self._L.mceik_mcmc_fit_enable(self._h, C.byref(o))
+        if rc != 0:
+            raise (ValueError if rc == 1 else RuntimeError)(
+                f"mceik_mcmc_fit_enable failed ({rc}): tick a power of two, nbins even in [2, 256], zmax > 0, a finite "
+                "t0_ref, and no held sums of other options")
+        self._fit = (float(tick), int(nbins), float(zmax), ref.copy())
+        self._fit_active = True
+
+    def fit_disable(self):
+        """Stop accumulating; the sums stay (`fit_raw`, `fit_partials`, a later `fit_enable` of the same options)."""
+        if self._L.mceik_mcmc_fit_disable(self._h) != 0:
+            raise RuntimeError("mceik_mcmc_fit_disable failed")
+        self._fit_active = False
+
+    def fit_clear(self):
+        """Drop the sums."""
+        if self._L.mceik_mcmc_fit_clear(self._h) != 0:
+            raise RuntimeError("mceik_mcmc_fit_clear failed")
+        self._fit = None
+        self._fit_active = False
+
+    def _fit_on(self):
+        if self._fit is None:
+            raise RuntimeError("the data-fit sums are not enabled (Sampler.fit_enable)")
+        return self._fit
+
+    def fit_accumulate(self):
+        """Add the cold chains' current state to the sums now (enqueued)."""
+        self._fit_on()
+        rc = self._L.mceik_mcmc_fit_accumulate(self._h)
+        if rc != 0:
+            raise RuntimeError(f"mceik_mcmc_fit_accumulate failed ({rc})")
+
+    def _fit_arrays(self):
+        nbins = self._fit_on()[1]
+        p = self.p
+        nobs, nev = len(p.tobs), p.nevents
+        return {"sq": ((nobs,), np.int64), "szq": ((nobs,), np.int64), "sq2": ((nobs, 2), np.uint64),
+                "szq2": ((nobs, 2), np.uint64), "stq": ((nev,), np.int64), "stq2": ((nev, 2), np.uint64),
+                "hist": ((max(1, p.nphase), p.nstat, nbins), np.int64), "sat": ((3,), np.int64)}
+
+    def fit_raw(self):
+        """The accumulators as host arrays: {"n": states per chain, "tick",
+        "nbins", "zmax", "t0_ref" [nev], "sq", "szq" int64 [nobs], "sq2", "szq2"
+        uint64 [nobs, 2] (lo, hi words), "stq" int64 [nev], "stq2" uint64 [nev,
+        2], "hist" int64 [nphase, nstat, nbins], "sat" int64 [3] (clamped q,
+        zq, tq)}."""
+        tick, nbins, zmax, ref = self._fit_on()
+        out = {k: np.zeros(sh, dt) for k, (sh, dt) in self._fit_arrays().items()}
+        n = C.c_longlong(0)
+        rc = self._L.mceik_mcmc_fit_get(self._h, C.byref(n), *(out[k].ctypes.data_as(C.c_void_p) for k in out))
+        if rc != 0:
+            raise RuntimeError(f"mceik_mcmc_fit_get failed ({rc})")
+        out.update({"n": n.value, "tick": tick, "nbins": nbins, "zmax": zmax, "t0_ref": ref.copy()})
+        return out
+
+    def _fit_set(self, raw):
+        arr = {k: np.ascontiguousarray(raw[k], dtype=dt) for k, (sh, dt) in self._fit_arrays().items()}
+        assert all(arr[k].shape == sh for k, (sh, dt) in self._fit_arrays().items())
+        rc = self._L.mceik_mcmc_fit_set(self._h, int(raw["n"]), *(arr[k].ctypes.data_as(C.c_void_p) for k in arr))
+        if rc != 0:
+            raise RuntimeError(f"mceik_mcmc_fit_set failed ({rc})")
+
+    def fit_partials(self):
+        """The pooled sums as exact partials (`FitPartials`): what ranks exchange and merge."""
+        tick, nbins, zmax, ref = self._fit_on()
+        p = self.p
+        out = FitPartials(len(p.tobs), p.nevents, max(1, p.nphase), p.nstat, nbins, tick, zmax)
+        st = out._struct()
+        rc = self._L.mceik_mcmc_fit_partials(self._h, C.byref(st))
+        if rc != 0:
+            raise RuntimeError(f"mceik_mcmc_fit_partials failed ({rc})")
+        out.nchains, out.nkept = int(st.nchains), int(st.nkept)
+        out.sat[:] = list(st.sat)
+        return out
+
+    def fit_last(self):
+        """The last kept step's integers of every chain: (q, zq int32 [nchains,
+        nobs], tq int32 [nchains, nev]); q, zq are 0 for a masked pick, rows of
+        chains that are not cold stay 0."""
+        self._fit_on()
+        q = np.zeros((self.nchains, len(self.p.tobs)), np.int32)
+        zq, tq = np.zeros_like(q), np.zeros((self.nchains, self.p.nevents), np.int32)
+        rc = self._L.mceik_mcmc_fit_last(self._h, *(a.ctypes.data_as(C.c_void_p) for a in (q, zq, tq)))
+        if rc != 0:
+            raise RuntimeError(f"mceik_mcmc_fit_last failed ({rc})")
+        return q, zq, tq
+
     def fsm_stats(self, reset=False):
         """(FSM kernel ms from hipEvents, launches, executed iterations summed over
         solves, (brick visits, column segments updated, segments changed, wave macro
@@ -1846,6 +1971,106 @@ def ess_summary(smp: Sampler, group=None, level=None, dst=0):
     return None if parts is None else EssSummary(parts, level)
 
 
+def fit_check(tick, rmax):
+    """Residuals (and origin times less t0_ref) up to `rmax` seconds fit the
+    32-bit words of `fit_enable` at `tick` (mceik_fit_check: tick a power of
+    two and rmax / tick <= 2^31 - 1)."""
+    return _lib.lib().mceik_fit_check(float(tick), float(rmax)) == 0
+
+
+class FitPartials:
+    """Host arrays of mceik_fit_partials (include/mceik.h): sq, szq int64
+    [nobs] (sums of the residuals in ticks and of 1024 z), sq2, szq2 uint64
+    [nobs, 2] (lo, hi words of the 128-bit sums of their squares), stq int64
+    [nev] and stq2 uint64 [nev, 2] (the origin times less t0_ref), hist int64
+    [nphase, nstat, nbins], sat int64 [3] (clamped values), over `nchains`
+    chains of `nkept` states each; obs_ptr, obs_stat, obs_phase, obs_mask and
+    t0_ref say what the rows are.  Exact integers: partials of shards or ranks
+    merge by addition, in any order.  Plain attributes, so it travels as a
+    host object (pickle)."""
+
+    def __init__(self, nobs, nev, nphase, nstat, nbins, tick, zmax, nchains=0, nkept=0):
+        self.nobs, self.nev, self.nphase, self.nstat, self.nbins = int(nobs), int(nev), int(nphase), int(nstat), int(nbins)
+        self.tick, self.zmax = float(tick), float(zmax)
+        self.nchains, self.nkept = int(nchains), int(nkept)
+        self.obs_ptr = np.zeros(self.nev + 1, np.int32)
+        self.obs_stat, self.obs_phase, self.obs_mask = (np.zeros(self.nobs, np.int32) for _ in range(3))
+        self.t0_ref = np.zeros(self.nev, np.float64)
+        self.sq, self.szq = np.zeros(self.nobs, np.int64), np.zeros(self.nobs, np.int64)
+        self.sq2, self.szq2 = np.zeros((self.nobs, 2), np.uint64), np.zeros((self.nobs, 2), np.uint64)
+        self.stq, self.stq2 = np.zeros(self.nev, np.int64), np.zeros((self.nev, 2), np.uint64)
+        self.hist = np.zeros((self.nphase, self.nstat, self.nbins), np.int64)
+        self.sat = np.zeros(3, np.int64)
+
+    def _struct(self):
+        st = _lib.FitPartials()
+        st.nobs, st.nev, st.nphase, st.nstat, st.nbins = self.nobs, self.nev, self.nphase, self.nstat, self.nbins
+        st.tick, st.zmax = self.tick, self.zmax
+        st.nchains, st.nkept = self.nchains, self.nkept
+        for name in ("obs_ptr", "obs_stat", "obs_phase", "obs_mask", "t0_ref", "sq", "szq", "sq2", "szq2", "stq", "stq2",
+                     "hist"):
+            setattr(st, name, getattr(self, name).ctypes.data)
+        for k in range(3):
+            st.sat[k] = int(self.sat[k])
+        return st
+
+    def merge(self, other):
+        """self += other (mceik_fit_merge); both must hold the same
+        observations, options and states per chain."""
+        a, b = self._struct(), other._struct()
+        if _lib.lib().mceik_fit_merge(C.byref(a), C.byref(b)) != 0:
+            raise ValueError("data-fit partials do not match (observations, tick, nbins, zmax, t0_ref, nkept)")
+        self.nchains = int(a.nchains)
+        self.sat[:] = list(a.sat)
+        return self
+
+    def finish(self):
+        """dict of float64 arrays (mceik_fit_finish): pick_mean, pick_sd,
+        pick_zmean, pick_zrms [nobs]; t0_mean, t0_sd, ev_misfit [nev];
+        sta_mean, sta_zrms [nphase, nstat]; phase_zrms [nphase]."""
+        out = {k: np.empty(self.nobs) for k in ("pick_mean", "pick_sd", "pick_zmean", "pick_zrms")}
+        out.update({k: np.empty(self.nev) for k in ("t0_mean", "t0_sd", "ev_misfit")})
+        out.update({k: np.empty((self.nphase, self.nstat)) for k in ("sta_mean", "sta_zrms")})
+        out["phase_zrms"] = np.empty(self.nphase)
+        st = self._struct()
+        rc = _lib.lib().mceik_fit_finish(C.byref(st), *(a.ctypes.data_as(C.c_void_p) for a in out.values()))
+        if rc != 0:
+            raise RuntimeError(f"mceik_fit_finish failed ({rc})")
+        return out
+
+
+class FitSummary:
+    """The data side of a run from merged `FitPartials`.  Per pick [nobs]:
+    `pick_mean`, `pick_sd` (seconds) of the residual tobs - tcorr - (te + t0)
+    and `pick_zmean`, `pick_zrms` of the standardised residual z (rms about 1
+    where the noise level is right).  Per event [nev]: `t0_mean`, `t0_sd` (the
+    origin time, t0_ref added back) and `ev_misfit`, the mean over states of
+    sum z^2 / (used picks - 1).  Per (phase, station) [nphase, nstat]:
+    `sta_mean` (the mean residual: the data's estimate of a station static),
+    `sta_zrms` and `hist` [nphase, nstat, nbins], the counts of z over
+    `bin_edges` (the edge bins take the tails).  `phase_zrms` [nphase];
+    `saturated` = (q, zq, tq) values that were clamped (0 in a healthy run).
+    NaN: a masked pick, a row or event without used picks, fewer than 2
+    states.  `count` states per chain over `nchains` chains."""
+
+    def __init__(self, parts: FitPartials):
+        for k, v in parts.finish().items():
+            setattr(self, k, v)
+        self.hist = parts.hist.copy()
+        self.bin_edges = np.linspace(-parts.zmax, parts.zmax, parts.nbins + 1)
+        self.saturated = tuple(int(x) for x in parts.sat)
+        self.tick, self.count, self.nchains = parts.tick, parts.nkept, parts.nchains
+
+
+def fit_summary(smp: Sampler, group=None, dst=0):
+    """`FitSummary` of a sampler's data-fit sums.  With a torch.distributed
+    `group` the ranks' exact partials are gathered as host objects and merged
+    on rank `dst`, which gets the summary of all chains; the other ranks get
+    None (as `posterior_summary`)."""
+    parts = _gather_merged(smp.fit_partials(), group, dst)
+    return None if parts is None else FitSummary(parts)
+
+
 def picks_from_forward(device=0, precision=64):
     """picks callable for make_problem: GPU forward of the true model (fp64 by
     default: the reference's arithmetic, and a different kernel instance from
@@ -1865,10 +2090,10 @@ def picks_from_forward(device=0, precision=64):
     return f
 
 
-def _pick_terms(p: Problem, ttab, var, tcorr):
+def _pick_terms(p: Problem, ttab, var, tcorr, with_t0=False):
     """event_obj's arithmetic (csrc/mcmc_device.h) on the host, operation for
     operation in fp64: per event the used picks, their weights 1 / var, xnorm,
-    the residuals tc - (te + t0) and objfn."""
+    the residuals tc - (te + t0) and objfn (with_t0: and, sixth, t0)."""
     tt = np.asarray(ttab, dtype=np.float32).astype(np.float64).reshape(max(1, p.nphase), p.nstat, p.nevents)
     var = np.asarray(p.var if var is None else var, dtype=np.float64)
     tcorr = np.asarray(p.tcorr if tcorr is None else tcorr, dtype=np.float64)
@@ -1891,7 +2116,7 @@ def _pick_terms(p: Problem, ttab, var, tcorr):
             s = ((1.0 / float(var[j])) * sqrt2i) * r
             obj = obj + s * s
             res.append(r)
-        out.append((js, [1.0 / float(var[j]) for j in js], xnorm, res, obj))
+        out.append((js, [1.0 / float(var[j]) for j in js], xnorm, res, obj) + ((t0,) if with_t0 else ()))
     return out
 
 
