@@ -1054,6 +1054,97 @@ double mceik_det_exp(double x);
 int mceik_lang_cell(uint32_t seed, uint32_t gchain, uint64_t step, int cell, double d, int v, int vlo, int vhi,
                     double sigma, int dmax, int *delta, int *lo, int *hi, double *logq);
 
+/* ---- differential-evolution (population) moves (csrc/de.hip)
+ * Off by default; with it off nothing changes.  The chains of a sampler all
+ * sample the same posterior, so the spread of their current states estimates
+ * its scale and correlations.  A DE step (DE-MC, ter Braak 2006, with the
+ * crossover of DREAM, Vrugt et al. 2009) proposes v + gamma (v_a - v_b) on one
+ * phase model of a chain from two other chains a, b.  It moves a whole model,
+ * it is symmetric (no gradient, no Hastings term) and it costs one forward per
+ * moving chain, as a single-cell step does.  Everything up to the accept test
+ * is integer arithmetic, so the proposal is symmetric exactly.
+ *
+ * Options: every, offset; gq = gamma_q16 = round(gamma * 65536) in [1, 131072];
+ * crq = cr_q16 = round(cr * 65536) in [1, 65536] (cr: the probability that a
+ * cell takes part).
+ *
+ * Global step gs is a DE step iff gs % every == offset and it is neither a
+ * hypocentre, a nuisance nor a Langevin step; it replaces that step's velocity
+ * proposal.  A swap round that falls on the step runs first.  DE step k = (gs
+ * - offset) / every has parity par = k & 1 and phase ph = (k >> 1) % nphase,
+ * common to all chains.
+ *   populations  the population of a chain is its temperature rung on this
+ *              sampler: rung r holds local chains r * G + g, g in [0, G)
+ *              (untempered: one rung, G = nchains).  Chains with (g & 1) == par
+ *              are the step's movers; the others of the rung, ordered by g, are
+ *              its partner set of nb members and stand still: no proposal, no
+ *              forward, accept = 0, state, logL and naccept untouched.  (Movers
+ *              that read each other while both move would not leave the product
+ *              posterior invariant; with the partner set fixed each mover's
+ *              kernel is a symmetric Metropolis kernel for a fixed pair set.)
+ *   step draw  of mover c (global id g): r = Philox4x32-10(counter {(uint32)gs,
+ *              (uint32)(gs >> 32), 5, 0xFFFFFFFF}, key {g, seed})
+ *              (counter word 2: proposals 0, swaps 1, hypocentres 2, nuisance
+ *              moves 3, Langevin 4);  i = (r0 * nb) >> 32;  j = (r1 * (nb - 1))
+ *              >> 32, j += (j >= i);  r2 & 1: i and j swap;  a, b = the i-th and
+ *              j-th members of the partner set;  log u = det_log((r3 + 0.5) / 2^32)
+ *   cell n     of phase ph: w = word n & 3 of Philox(counter {.., .., 5, n >> 2});
+ *              the cell takes part iff (w >> 16) < crq; then with d = v_a[n] -
+ *              v_b[n] and rr = w & 0xFFFF
+ *                delta = (2 * gq * d + 2 * rr + 1) >> 17    (int64, arithmetic shift)
+ *              = floor((gq d + rr + 0.5) / 65536), else delta = 0.  The numerator
+ *              is odd, so delta(d, rr) == -delta(-d, 65535 - rr) always: with the
+ *              swap bit the reverse move is exactly as likely as the move.
+ *              v' = v + delta on phase ph; the other phase does not change.
+ *   box        a cell of v' outside [vmin, vmax] (phase 1: [vsmin, vsmax])
+ *              rejects the whole move (clamping a cell, or leaving it unmoved,
+ *              would not be symmetric).  Its forward still runs -- on v' with
+ *              those cells left at v -- and is never read; logL' is reported
+ *              as logL.
+ *   accept iff v' is inside the box, no unskipped solve of the mover failed
+ *              (ierr) and log u < beta * (logL' - logL), log u folded with the
+ *              exact differences of the prior's full integer energies of v'
+ *              and v when the prior is on; logL' honours moved hypocentres,
+ *              noise scale and statics.
+ * A kept step keeps every chain, standing ones included.  After a DE step
+ * mceik_mcmc_last's accept is 0 for standing chains, only the movers' table
+ * rows are the step's, and mceik_mcmc_last_phase is ph for all chains.
+ * Whether the move pays in effective samples per second depends on the
+ * problem; tools/ess_compare.py measures it.
+ *
+ * enable returns 1 (with a message) on a population of fewer than 4 chains,
+ * every < 1, an offset outside [0, every), gq or crq out of range; tempering
+ * cannot be switched to rungs of fewer than 4 chains while DE moves are on.
+ * While enabled every step is one launch of each kernel (mceik_mcmc_info.
+ * multi_step reports 0 until disable).  The other functions return 1 before
+ * the first enable.  Every function returns 0, 1 on invalid arguments or -1 on
+ * a device failure. */
+typedef struct mceik_de_opts { int every, offset, gamma_q16, cr_q16; } mceik_de_opts;
+/* Turns the moves on (or replaces the options); resets the counters.  Synchronises. */
+int mceik_mcmc_de_enable(mceik_mcmc *s, const mceik_de_opts *o);
+/* Later steps are the sampler's other velocity proposals again. */
+int mceik_mcmc_de_disable(mceik_mcmc *s);
+/* The options in force (every = 0 after disable; o may be NULL). */
+int mceik_mcmc_de_get(mceik_mcmc *s, mceik_de_opts *o);
+/* Over the chains: DE moves tried, accepted, rejected for leaving the box,
+ * failed (a solve's ierr), and cells with delta != 0 of the accepted moves.
+ * Any may be NULL.  Synchronises. */
+int mceik_mcmc_de_stats(mceik_mcmc *s, long long *attempts, long long *accepts, long long *outbox, long long *failed,
+                        long long *moved, int reset);
+/* The last DE step: mover [nchains] (1: the chain moved), a, b [nchains] (the
+ * partners as local chains; -1 for standing chains), *phase (-1: no DE step
+ * yet), nmove [nchains] (cells with delta != 0), inbox, status (1: failed),
+ * logL' [nchains] (logL where the move left the box or failed; 0 for standing
+ * chains), accept [nchains].  Any may be NULL.  Synchronises. */
+int mceik_mcmc_de_last(mceik_mcmc *s, int *mover, int *a, int *b, int *phase, int *nmove, int *inbox, int *status,
+                       double *logl_prop, unsigned char *accept);
+/* Host only (no GPU call), the arithmetic the kernels run.  de_delta: the move
+ * of a cell whose partners differ by d under the cell's word; 1 on gq or crq
+ * out of range.  de_draw: the ordered pair i != j in [0, nb) and log u of
+ * global chain gchain at global step `step`; 1 on nb < 2. */
+int mceik_de_delta(int gq, int d, uint32_t word, int crq, int *delta);
+int mceik_de_draw(uint32_t seed, uint32_t gchain, uint64_t step, int nb, int *i, int *j, double *logu);
+
 #ifdef __cplusplus
 }
 #endif

@@ -133,6 +133,11 @@ class NuisOpts(C.Structure):
                 ("lam", C.c_void_p), ("lnlam", C.c_void_p), ("norm", C.c_void_p)]
 
 
+class DeOpts(C.Structure):
+    """mceik_de_opts (include/mceik.h)."""
+    _fields_ = [("every", C.c_int), ("offset", C.c_int), ("gamma_q16", C.c_int), ("cr_q16", C.c_int)]
+
+
 class LangOpts(C.Structure):
     """mceik_lang_opts (include/mceik.h)."""
     _fields_ = [("every", C.c_int), ("offset", C.c_int), ("sigma", C.c_double), ("dmax", C.c_int),
@@ -233,6 +238,8 @@ EXPORTS = ("eikonal3d_serial_driver", "eikonal3d_serial_driver_sp", "eikonal3d_b
            "mceik_fit_check", "mceik_fit_merge", "mceik_fit_finish",
            "mceik_mcmc_lang_enable", "mceik_mcmc_lang_disable", "mceik_mcmc_lang_get", "mceik_mcmc_lang_stats",
            "mceik_mcmc_lang_last", "mceik_det_exp", "mceik_lang_cell",
+           "mceik_mcmc_de_enable", "mceik_mcmc_de_disable", "mceik_mcmc_de_get", "mceik_mcmc_de_stats",
+           "mceik_mcmc_de_last", "mceik_de_delta", "mceik_de_draw",
            "mceik_parms_defaults", "mceik_parms_set", "mceik_parms_read", "mceik_parms_args", "mceik_parms_write",
            "mceik_comm_available", "mceik_comm_unique_id", "mceik_comm_init", "mceik_comm_finalize", "mceik_mcmc_gather",
            "os_path_exists", "os_path_isdir", "os_path_isfile", "os_makedirs", "os_mkdir")
@@ -385,6 +392,20 @@ def lib():
     L.mceik_lang_cell.restype = C.c_int
     L.mceik_lang_cell.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int,
                                   C.c_double, C.c_int, pi, pi, pi, C.c_void_p]
+    L.mceik_mcmc_de_enable.restype = C.c_int
+    L.mceik_mcmc_de_enable.argtypes = [C.c_void_p, C.POINTER(DeOpts)]
+    L.mceik_mcmc_de_disable.restype = C.c_int
+    L.mceik_mcmc_de_disable.argtypes = [C.c_void_p]
+    L.mceik_mcmc_de_get.restype = C.c_int
+    L.mceik_mcmc_de_get.argtypes = [C.c_void_p, C.POINTER(DeOpts)]
+    L.mceik_mcmc_de_stats.restype = C.c_int
+    L.mceik_mcmc_de_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_longlong)] * 5 + [C.c_int]
+    L.mceik_mcmc_de_last.restype = C.c_int
+    L.mceik_mcmc_de_last.argtypes = [C.c_void_p] * 10
+    L.mceik_de_delta.restype = C.c_int
+    L.mceik_de_delta.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_int, pi]
+    L.mceik_de_draw.restype = C.c_int
+    L.mceik_de_draw.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, pi, pi, C.POINTER(C.c_double)]
     L.mceik_mcmc_prior_enable.restype = C.c_int
     L.mceik_mcmc_prior_enable.argtypes = [C.c_void_p, C.POINTER(PriorOpts)]
     L.mceik_mcmc_prior_disable.restype = C.c_int

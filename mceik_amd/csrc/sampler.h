@@ -10,6 +10,7 @@
 #include "../../include/mceik.h"
 #include "block.h"
 #include "cov.h"
+#include "de.h"
 #include "ess.h"
 #include "fit.h"
 #include "fsm_common.h"
@@ -23,7 +24,7 @@
 #define MCEIK_MAX_PIPES 4
 #define MCEIK_ITERS_N (6 + MCEIK_TRAFFIC_N)   // d_iters: iterations, 4 visit statistics, solves, traffic
 
-// A pipe: a part of the chains stepped on a stream of its own.  D, B, P, H, N, L, fb
+// A pipe: a part of the chains stepped on a stream of its own.  D, B, P, H, N, L, De, fb
 // and fb_hyp are views of the sampler's restricted to the pipe's chains;
 // pipes_refresh alone writes them.  (The accumulators of kept states --
 // posterior, covariances, batch means, data fit -- have no views: their
@@ -35,6 +36,7 @@ struct Pipe {
     HypoDev H;
     NuisDev N;
     LangDev L;                         // (arrays null before the first lang_enable)
+    DeDev De;                          // (arrays null before the first de_enable)
     mceik_fsm_batch fb;
     mceik_fsm_batch fb_hyp;            // a hypocentre step's batch (every model of the pipe's chains)
     void *ws;                          // the pipe's workspace: a part of the sampler's ws, ws itself, or its own
@@ -165,6 +167,19 @@ struct mceik_mcmc {
     size_t lang_mem;
     LangDev L;
     LangPipe lang_pipe[MCEIK_MAX_PIPES];
+    // Differential-evolution moves (de.hip); off by default.
+    // De's arrays are null until the first enable, which allocates everything a
+    // step uses.  While on, every step takes the per-step branch; plan_step says
+    // which steps are DE steps, their parity and their phase.  d_demov: both
+    // parities' mover lists of the whole sampler, ascending (de_lists rebuilds
+    // them when the populations change: enable, tempering on / off); a pipe's
+    // lists are the parts that fall on its chains.
+    bool de_on;
+    int de_every, de_offset;
+    DeDev De;
+    int *d_demov;                      // [2][nchains]
+    std::vector<int> de_mov[2];        // the host's copy
+    int de_last_ph;                    // the last DE step's phase (-1: none yet)
     hipStream_t stream;
     void *ws;
     size_t ws_bytes;
@@ -202,12 +217,12 @@ int temper_round(mceik_mcmc *s, int parity);
 // fold sits between a step's proposal and its forward); hypocentre moves (a
 // hypocentre step has kernels and a batch of its own); held nuisance state (it
 // enters every logL, which the multi-step kernel's epilogue does not know);
-// Langevin moves (a Langevin step is a pipeline of launches of its own); the
+// Langevin moves and DE moves (such a step is a pipeline of launches of its own); the
 // data-fit sums of a one-model sampler (they read the chains' current tables,
 // which the multi-step kernel's epilogue keeps for two models only).
 static inline bool mcmc_multi_step(const mceik_mcmc *s)
 {
-    return s->persist && !s->block_on && !s->prior_on && !s->hypo_on && !s->N.kn && !s->lang_on &&
+    return s->persist && !s->block_on && !s->prior_on && !s->hypo_on && !s->N.kn && !s->lang_on && !s->de_on &&
            !(s->fit_on && s->D.nphase == 1);
 }
 // A one-model sampler's current tables (sampler_api.hip).  hold: while nuisance
@@ -222,6 +237,9 @@ int mcmc_tables1_drop(mceik_mcmc *s);
 // pick weights (evw) and the adjoint's per-solve rows (gs), each a multiple of
 // 256; returns their sum.
 size_t lang_pipe_bytes(const mceik_mcmc *s, int k, int m, size_t *u, size_t *fws, size_t *aws, size_t *evw, size_t *gs);
-// Recomputes every pipe's D, B, P, H, N, L and fb from the sampler's (and a multi-step
-// sampler's device copy of D): call after any change to s->D, s->B, s->P, s->H, s->N, s->L or s->fb.
+// The DE mover lists for the populations in force (G = temper_cold); uploads
+// them and refreshes the pipes.  No-op before the first de_enable.  Synchronises.
+int de_lists(mceik_mcmc *s);
+// Recomputes every pipe's D, B, P, H, N, L, De and fb from the sampler's (and a multi-step
+// sampler's device copy of D): call after any change to s->D, s->B, s->P, s->H, s->N, s->L, s->De or s->fb.
 int pipes_refresh(mceik_mcmc *s);

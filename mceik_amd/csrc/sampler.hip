@@ -4,8 +4,8 @@
 //
 // Host orchestration only.  The numerics live in fsm_kernel.hip,
 // fsm16_kernel.hip, mcmc_kernels.hip, temper.hip, block.hip, prior.hip,
-// hypo.hip, nuis.hip, lang.hip, adjoint.hip, posterior.hip, cov.hip, ess.hip
-// and fit.hip.
+// hypo.hip, nuis.hip, lang.hip, de.hip, adjoint.hip, posterior.hip, cov.hip,
+// ess.hip and fit.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -63,8 +63,9 @@ static hipStream_t pipe_stream(const mceik_mcmc *s, int k) { return s->npipe > 1
 
 // The FSM launch of pipe k's batch on its stream: the step batch, or with hyp
 // the hypocentre step's (every model of the pipe's chains at [current |
-// candidate]).
-static int mcmc_forward(mceik_mcmc *s, bool timed, int k, const McmcExt *ext = nullptr, bool hyp = false)
+// candidate]), or `other` in the pipe's workspace (a DE step's compact batch).
+static int mcmc_forward(mceik_mcmc *s, bool timed, int k, const McmcExt *ext = nullptr, bool hyp = false,
+                        const mceik_fsm_batch *other = nullptr)
 {
     Pipe &p = s->pipe[k];
     const hipStream_t st = pipe_stream(s, k);
@@ -83,13 +84,13 @@ static int mcmc_forward(mceik_mcmc *s, bool timed, int k, const McmcExt *ext = n
         }
         HIPCHK(hipEventRecord(s->ev[2 * r], st));
     }
-    if (fsm_batch_solve_impl(hyp ? &p.fb_hyp : &p.fb, p.ws, p.ws_bytes, st, ext)) return -1;
+    if (fsm_batch_solve_impl(other ? other : hyp ? &p.fb_hyp : &p.fb, p.ws, p.ws_bytes, st, ext)) return -1;
     s->last_ttab = s->fb.ttab;
     if (timed) {
         HIPCHK(hipEventRecord(s->ev[2 * r + 1], st));
         s->nlaunch++;
     }
-    if (s->d_order && s->npipe == 1 && !hyp) {  // the next launch pulls this launch's longest solves first (one pipe only)
+    if (s->d_order && s->npipe == 1 && !hyp && !other) {  // the next launch pulls this launch's longest solves first (one pipe only)
         HIPCHK(mcmc_lpt_order(s->d_clock, p.fb.nmodel * p.fb.nstat, s->d_order, st));
         // the batch the next launch uses, and the sampler's, which pipes_refresh derives it from
         p.fb.solve_order = s->fb.solve_order = s->d_order;
@@ -205,6 +206,35 @@ static LangDev dev_view(const LangDev &L, const McmcDev &D, int off)
     return V;
 }
 
+// The same view of the DE state's per-chain arrays; the compact buffers of the
+// pipe's movers start at the pipe's own rows (a pipe has at most as many movers
+// as chains), its mover lists are the parts of the sampler's that fall on its
+// chains (movs: the host's copy of those).
+static DeDev dev_view(const DeDev &L, const McmcDev &D, const mceik_fsm_batch &fb, const std::vector<int> *movs,
+                      const int *d_mov, int off, int n)
+{
+    DeDev V = L;
+    if (!L.a) return V;
+    const size_t o = (size_t)off, os = o * D.nstat;
+    V.off = off;
+    V.a += o; V.b += o; V.inbox += o; V.nmove += o; V.status += o; V.logl_prop += o;
+    V.vprop += o * D.ncm;
+    V.pen += o * D.nphase;
+    V.cnt += 5 * o;
+    V.slow += o * D.ncell; V.ttab += os * D.nev; V.ierr += os; V.niter += os; V.ev += o * D.nev;
+    V.ttab_out = fb.ttab + os * D.nev;
+    V.ierr_out = fb.ierr + os;
+    V.niter_out = fb.niter + os;
+    for (int par = 0; par < 2; par++) {
+        const std::vector<int> &m = movs[par];
+        const size_t lo = std::lower_bound(m.begin(), m.end(), off) - m.begin();
+        const size_t hi = std::lower_bound(m.begin(), m.end(), off + n) - m.begin();
+        V.mov[par] = d_mov + (size_t)par * D.nchains + lo;
+        V.nmov[par] = (int)(hi - lo);
+    }
+    return V;
+}
+
 // Chains [off, off + n) of the hypocentre step's batch: nphase models per
 // chain.  It runs in the workspace of the pipe's step batch sb, so it keeps at
 // most that batch's resident waves (the workspace grows with the waves only).
@@ -255,6 +285,7 @@ int pipes_refresh(mceik_mcmc *s)
         p.H = dev_view(s->H, s->D, lo);
         p.N = dev_view(s->N, s->D, lo);
         p.L = dev_view(s->L, s->D, lo);
+        p.De = dev_view(s->De, s->D, s->fb, s->de_mov, s->d_demov, lo, n);
         if (s->H.hyp) p.fb_hyp = hyp_batch_view(s->fb_hyp, p.fb, lo, n, (size_t)s->D.ncm, s->D.nphase);
     }
     // the longest-first order covers the whole batch: one pipe's (mcmc_forward)
@@ -699,16 +730,19 @@ int temper_round(mceik_mcmc *s, int parity)
 
 // What global step gs is.  A step has one kind, by precedence: hypocentre (gs %
 // hypo_every == hypo_every - 1), else nuisance (gs % nuis_every == nuis_offset
-// while state is held), else Langevin (gs % lang_every == lang_offset), else a
-// velocity proposal.  A swap round belongs to step gs > 0 with gs % swap_every
-// == 0 and runs before its proposal, with parity (gs / swap_every) & 1.
-enum StepKind { STEP_VELOCITY, STEP_HYPO, STEP_NUIS, STEP_LANG };
+// while state is held), else Langevin (gs % lang_every == lang_offset), else DE
+// (gs % de_every == de_offset), else a velocity proposal.  A swap round belongs
+// to step gs > 0 with gs % swap_every == 0 and runs before its proposal, with
+// parity (gs / swap_every) & 1.  DE step k = (gs - de_offset) / de_every moves
+// the chains of parity k & 1 of every population on phase (k >> 1) % nphase.
+enum StepKind { STEP_VELOCITY, STEP_HYPO, STEP_NUIS, STEP_LANG, STEP_DE };
 
 struct StepPlan {
     StepKind kind;
     bool swap;
     int parity;
     bool kept;                         // kept_step(gs)
+    int de_par, de_ph;                 // STEP_DE: the movers' parity and the phase
 };
 
 static StepPlan plan_step(const mceik_mcmc *s, long long gs)
@@ -717,7 +751,11 @@ static StepPlan plan_step(const mceik_mcmc *s, long long gs)
     if (s->hypo_on && s->hypo_every > 0 && gs % s->hypo_every == s->hypo_every - 1) q.kind = STEP_HYPO;
     else if (s->nuis_on && s->N.kn && s->nuis_every > 0 && gs % s->nuis_every == s->nuis_offset) q.kind = STEP_NUIS;
     else if (s->lang_on && s->lang_every > 0 && gs % s->lang_every == s->lang_offset) q.kind = STEP_LANG;
+    else if (s->de_on && s->de_every > 0 && gs % s->de_every == s->de_offset) q.kind = STEP_DE;
     else q.kind = STEP_VELOCITY;
+    const long long dk = q.kind == STEP_DE ? (gs - s->de_offset) / s->de_every : 0;
+    q.de_par = (int)(dk & 1);
+    q.de_ph = (int)((dk >> 1) % s->D.nphase);
     q.swap = s->ntemps > 1 && s->swap_every > 0 && gs > 0 && gs % s->swap_every == 0;
     q.parity = q.swap ? (int)((gs / s->swap_every) & 1) : 0;
     q.kept = kept_step(s, gs);
@@ -842,6 +880,80 @@ static int lang_step(mceik_mcmc *s, int k, uint64_t step, int slot)
     return 0;
 }
 
+// The pipes join the sampler's stream and fork again: everything queued on any
+// pipe so far is ordered before everything queued on any pipe from here on.
+static int pipes_join_fork(mceik_mcmc *s)
+{
+    const int np = s->npipe;
+    if (np < 2) return 0;
+    for (int k = 0; k < np; k++) {
+        HIPCHK(hipEventRecord(s->pipe[k].join, s->pipe[k].st));
+        HIPCHK(hipStreamWaitEvent(s->stream, s->pipe[k].join, 0));
+    }
+    HIPCHK(hipEventRecord(s->pfork, s->stream));
+    for (int k = 0; k < np; k++) HIPCHK(hipStreamWaitEvent(s->pipe[k].st, s->pfork, 0));
+    return 0;
+}
+
+// The proposals of a DE step, every pipe's.  A proposal reads
+// the partners' models, which may be another pipe's chains: the pipes join and
+// fork before it (a swap round of the same step has done that already), and no
+// pipe goes on before every pipe's proposal has run, so nothing of this or a
+// later step writes a model that a proposal still reads.
+static int de_proposals(mceik_mcmc *s, uint64_t step, const StepPlan &q)
+{
+    const int np = s->npipe;
+    if (!q.swap && pipes_join_fork(s)) return -1;
+    for (int k = 0; k < np; k++) {
+        const Pipe &p = s->pipe[k];
+        HIPCHK(de_propose(p.D, p.H, p.De, step, q.de_par, q.de_ph, pipe_stream(s, k)));
+    }
+    if (pipes_join_fork(s)) return -1;
+    s->de_last_ph = q.de_ph;
+    return 0;
+}
+
+// The rest of pipe k's DE step: one forward of its movers' proposed models of
+// phase ph (the compact batch: a standing chain costs no solve), the tables
+// into the movers' rows of the step batch, the prior's full energies, the accept.
+static int de_step(mceik_mcmc *s, int k, const StepPlan &q, int slot)
+{
+    const Pipe &p = s->pipe[k];
+    const hipStream_t st = pipe_stream(s, k);
+    const McmcDev &D = p.D;
+    const DeDev &L = p.De;
+    const int nmov = L.nmov[q.de_par];
+    if (nmov > 0) {
+        mceik_fsm_batch b = batch_view(p.fb, 0, nmov, (size_t)s->D.ncm);
+        b.slow = L.slow;
+        b.model_phase = nullptr;
+        b.nphase = 1;
+        b.skip = s->fb.skip ? s->fb.skip + (size_t)q.de_ph * D.nstat : nullptr;
+        b.ttab = L.ttab;
+        b.ierr = L.ierr;
+        b.niter = L.niter;
+        if (b.ev_stride > 0) {
+            b.ev_node = L.ev;
+            b.ev_stride = D.nev;
+        }
+        b.solve_order = nullptr;
+        b.solve_clock = nullptr;
+        b.max_waves = ws_layout(&p.fb).nwaves;      // it runs in the step batch's workspace
+        if (mcmc_forward(s, true, k, nullptr, false, &b)) return -1;
+        HIPCHK(de_scatter(D, L, q.de_par, st));
+    }
+    if (s->prior_on) {                  // the full integer energies of v and v' (prior.hip's kernel adds into zeroed words)
+        const size_t ps = L.pen_stride, nb = (size_t)D.nchains * D.nphase * sizeof(unsigned long long);
+        for (int i = 0; i < 4; i++) HIPCHK(hipMemsetAsync(L.pen + i * ps, 0, nb, st));
+        McmcDev V = D;
+        V.v = L.vprop;                  // (a standing chain's row is stale: its energies are never read)
+        HIPCHK(prior_energy(D, p.B, p.P, L.pen, L.pen + ps, st));
+        HIPCHK(prior_energy(V, p.B, p.P, L.pen + 2 * ps, L.pen + 3 * ps, st));
+    }
+    HIPCHK(de_accept(D, p.N, p.P, s->prior_on, L, q.de_par, q.de_ph, slot, st));
+    return 0;
+}
+
 // Steps of one call.  Returns -1 on a HIP failure; the caller joins the pipes
 // whatever happened, so the caller's stream is always ordered after every
 // kernel this call queued on the internal streams.
@@ -900,6 +1012,7 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
                 for (int k = 0; k < np; k++) HIPCHK(hipStreamWaitEvent(s->pipe[k].st, s->pfork, 0));
             }
         }
+        if (q.kind == STEP_DE && de_proposals(s, step, q)) return -1;
         for (int k = 0; k < np; k++) {
             const Pipe &p = s->pipe[k];
             const hipStream_t st = pipe_stream(s, k);
@@ -914,6 +1027,9 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
                 break;
             case STEP_LANG:         // every cell of one model moves along its gradient: two forwards, two adjoints
                 if (lang_step(s, k, step, slot)) return -1;
+                break;
+            case STEP_DE:           // half of every population moves a whole model along a difference of two others: one forward
+                if (de_step(s, k, q, slot)) return -1;
                 break;
             case STEP_VELOCITY:
                 HIPCHK(blk ? block_propose(p.D, p.B, step, st) : mcmc_propose(p.D, step, st));

@@ -1,7 +1,7 @@
 // sampler_api.hip -- the sampler's accessors of the C-ABI (include/mceik.h:
 // sync, state, checkpoint / restore, kept samples, info, FSM statistics) and
-// its parallel-tempering, block-proposal, prior, hypocentre, noise / statics
-// and Langevin entry points.
+// its parallel-tempering, block-proposal, prior, hypocentre, noise / statics,
+// Langevin and differential-evolution entry points.
 // The sampler itself is sampler.hip.
 #include <hip/hip_runtime.h>
 #include <float.h>
@@ -92,6 +92,11 @@ extern "C" int mceik_mcmc_temper_enable(mceik_mcmc *s, const mceik_temper_opts *
     for (int r = 0; r + 1 < nt; r++)
         if (!(o->beta[r + 1] > 0.0 && o->beta[r + 1] <= o->beta[r])) return 1;
     if (post_holds_states(s)) return 1;
+    if (s->de_on && nch / nt < 4) {
+        fprintf(stderr, "mceik_mcmc_temper_enable: DE moves are on and a rung would hold %d chains; a DE population "
+                        "needs 4\n", nch / nt);
+        return 1;
+    }
     DeviceScope dg(s->device);
     HIPCHK(hipStreamSynchronize(s->stream));
     if (!s->d_beta && (dalloc(s, &s->d_beta, nch) || dalloc(s, &s->d_tflag, nch) || dalloc(s, &s->d_tcnt, 2 * (size_t)nch)))
@@ -105,7 +110,7 @@ extern "C" int mceik_mcmc_temper_enable(mceik_mcmc *s, const mceik_temper_opts *
     s->ntemps = nt;
     s->swap_every = o->swap_every;
     s->D.beta = nt > 1 ? s->d_beta : nullptr;       // one rung is the untempered sampler
-    return pipes_refresh(s);            // D.beta changed
+    return s->De.a ? de_lists(s) : pipes_refresh(s);   // D.beta changed, and the DE populations with the rungs
 }
 
 extern "C" int mceik_mcmc_temper_disable(mceik_mcmc *s)
@@ -119,7 +124,7 @@ extern "C" int mceik_mcmc_temper_disable(mceik_mcmc *s)
     s->swap_every = 0;
     s->beta.clear();
     s->D.beta = nullptr;
-    return pipes_refresh(s);            // D.beta changed
+    return s->De.a ? de_lists(s) : pipes_refresh(s);   // D.beta changed, and the DE populations with the rungs
 }
 
 extern "C" int mceik_mcmc_temper_get(mceik_mcmc *s, int *ntemps, int *swap_every, double *beta)
@@ -992,6 +997,158 @@ extern "C" int mceik_lang_cell(uint32_t seed, uint32_t gchain, uint64_t step, in
     if (lo) *lo = S.lo;
     if (hi) *hi = S.hi;
     for (int k = S.lo; k <= S.hi && logq; k++) logq[k - S.lo] = lang_logq(S, k);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// differential-evolution moves (include/mceik.h mceik_mcmc_de_*)
+
+int de_lists(mceik_mcmc *s)
+{
+    if (!s->De.a) return 0;
+    const int nch = s->D.nchains, G = temper_cold(s);
+    for (int par = 0; par < 2; par++) {
+        s->de_mov[par].clear();
+        for (int c = 0; c < nch; c++)
+            if (((c % G) & 1) == par) s->de_mov[par].push_back(c);
+    }
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    for (int par = 0; par < 2; par++)
+        if (!s->de_mov[par].empty())
+            HIPCHK(hipMemcpy(s->d_demov + (size_t)par * nch, s->de_mov[par].data(), s->de_mov[par].size() * sizeof(int),
+                             hipMemcpyHostToDevice));
+    s->De.G = G;
+    return pipes_refresh(s);
+}
+
+extern "C" int mceik_mcmc_de_enable(mceik_mcmc *s, const mceik_de_opts *o)
+{
+    if (!s || !o) return 1;
+    if (o->every < 1 || o->offset < 0 || o->offset >= o->every) {
+        fprintf(stderr, "mceik_mcmc_de_enable: every >= 1 and 0 <= offset < every\n");
+        return 1;
+    }
+    if (o->gamma_q16 < 1 || o->gamma_q16 > MCEIK_DE_GQ_MAX || o->cr_q16 < 1 || o->cr_q16 > MCEIK_DE_CRQ_MAX) {
+        fprintf(stderr, "mceik_mcmc_de_enable: 1 <= gamma_q16 <= %d and 1 <= cr_q16 <= %d\n", MCEIK_DE_GQ_MAX,
+                MCEIK_DE_CRQ_MAX);
+        return 1;
+    }
+    if (temper_cold(s) < 4) {
+        fprintf(stderr, "mceik_mcmc_de_enable: a population (the chains of one temperature rung) has %d chains; a "
+                        "partner set needs two, so a population needs 4\n", temper_cold(s));
+        return 1;
+    }
+    const McmcDev &D = s->D;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    DeDev &L = s->De;
+    const size_t nch = D.nchains, ns = nch * D.nstat;
+    if (!L.a) {                        // every array or none: a failed enable leaves the sampler as it was
+        DeDev A;
+        memset(&A, 0, sizeof(A));
+        int *mov = nullptr;
+        if (dalloc(s, &A.a, nch) || dalloc(s, &A.b, nch) || dalloc(s, &A.inbox, nch) || dalloc(s, &A.nmove, nch) ||
+            dalloc(s, &A.status, nch) || dalloc(s, &A.logl_prop, nch) || dalloc(s, &A.vprop, nch * D.ncm) ||
+            dalloc(s, &A.pen, 4 * nch * D.nphase) || dalloc(s, &A.cnt, 5 * nch) || dalloc(s, &A.slow, nch * D.ncell) ||
+            dalloc(s, &A.ttab, ns * D.nev) || dalloc(s, &A.ierr, ns) || dalloc(s, &A.niter, ns) ||
+            dalloc(s, &A.ev, nch * D.nev) || dalloc(s, &mov, 2 * nch))
+            return -1;
+        A.pen_stride = nch * D.nphase;
+        A.skip = s->fb.skip;
+        A.vall = D.v;
+        L = A;
+        s->d_demov = mov;
+        s->de_last_ph = -1;
+    }
+    HIPCHK(hipMemset(L.cnt, 0, 5 * nch * 8));
+    L.gq = o->gamma_q16;
+    L.crq = o->cr_q16;
+    s->de_every = o->every;
+    s->de_offset = o->offset;
+    s->de_on = true;
+    return de_lists(s);
+}
+
+extern "C" int mceik_mcmc_de_disable(mceik_mcmc *s)
+{
+    if (!s) return 1;
+    s->de_on = false;                  // host state only: queued steps keep the kernels they were queued with
+    return 0;
+}
+
+extern "C" int mceik_mcmc_de_get(mceik_mcmc *s, mceik_de_opts *o)
+{
+    if (!s || !s->De.a) return 1;
+    if (o) {
+        o->every = s->de_on ? s->de_every : 0;
+        o->offset = s->de_offset;
+        o->gamma_q16 = s->De.gq;
+        o->cr_q16 = s->De.crq;
+    }
+    return 0;
+}
+
+extern "C" int mceik_mcmc_de_stats(mceik_mcmc *s, long long *attempts, long long *accepts, long long *outbox,
+                                   long long *failed, long long *moved, int reset)
+{
+    if (!s || !s->De.a) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    const size_t nch = s->D.nchains;
+    std::vector<unsigned long long> cnt(5 * nch);
+    HIPCHK(hipMemcpy(cnt.data(), s->De.cnt, cnt.size() * 8, hipMemcpyDeviceToHost));
+    long long t[5] = {0, 0, 0, 0, 0};
+    for (size_t c = 0; c < nch; c++)
+        for (int q = 0; q < 5; q++) t[q] += (long long)cnt[5 * c + q];
+    if (attempts) *attempts = t[0];
+    if (accepts) *accepts = t[1];
+    if (outbox) *outbox = t[2];
+    if (failed) *failed = t[3];
+    if (moved) *moved = t[4];
+    if (reset) HIPCHK(hipMemset(s->De.cnt, 0, cnt.size() * 8));
+    return 0;
+}
+
+extern "C" int mceik_mcmc_de_last(mceik_mcmc *s, int *mover, int *a, int *b, int *phase, int *nmove, int *inbox,
+                                  int *status, double *logl_prop, unsigned char *accept)
+{
+    if (!s || !s->De.a) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    const size_t nch = s->D.nchains;
+    const DeDev &L = s->De;
+    std::vector<int> ha(nch);
+    HIPCHK(hipMemcpy(ha.data(), L.a, nch * sizeof(int), hipMemcpyDeviceToHost));
+    for (size_t c = 0; c < nch && mover; c++) mover[c] = s->de_last_ph >= 0 && ha[c] >= 0;
+    if (a) memcpy(a, ha.data(), nch * sizeof(int));
+    if (b) HIPCHK(hipMemcpy(b, L.b, nch * sizeof(int), hipMemcpyDeviceToHost));
+    if (phase) *phase = s->de_last_ph;
+    if (nmove) HIPCHK(hipMemcpy(nmove, L.nmove, nch * sizeof(int), hipMemcpyDeviceToHost));
+    if (inbox) HIPCHK(hipMemcpy(inbox, L.inbox, nch * sizeof(int), hipMemcpyDeviceToHost));
+    if (status) HIPCHK(hipMemcpy(status, L.status, nch * sizeof(int), hipMemcpyDeviceToHost));
+    if (logl_prop) HIPCHK(hipMemcpy(logl_prop, L.logl_prop, nch * 8, hipMemcpyDeviceToHost));
+    if (accept) HIPCHK(hipMemcpy(accept, s->D.accept, nch, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int mceik_de_delta(int gq, int d, uint32_t word, int crq, int *delta)
+{
+    if (gq < 1 || gq > MCEIK_DE_GQ_MAX || crq < 1 || crq > MCEIK_DE_CRQ_MAX || !delta) return 1;
+    const long long x = de_delta(gq, (long long)d, word, crq);
+    if (x < INT_MIN || x > INT_MAX) return 1;
+    *delta = (int)x;
+    return 0;
+}
+
+extern "C" int mceik_de_draw(uint32_t seed, uint32_t gchain, uint64_t step, int nb, int *i, int *j, double *logu)
+{
+    if (nb < 2) return 1;
+    int a, b;
+    const uint32_t r3 = de_draw(seed, gchain, step, nb, &a, &b);
+    if (i) *i = a;
+    if (j) *j = b;
+    if (logu) *logu = hypo_det_log_host(((double)r3 + 0.5) * (1.0 / 4294967296.0));
     return 0;
 }
 

@@ -436,6 +436,44 @@ def lang_cell(seed, gchain, step, cell, d, v, vlo, vhi, sigma, dmax):
     return delta.value, lo.value, logq[:hi.value - lo.value + 1].copy()
 
 
+DE_GQ_MAX, DE_CRQ_MAX = 131072, 65536
+
+
+def de_delta(gq, d, word, crq=DE_CRQ_MAX):
+    """The DE move of one cell (mceik_de_delta; host only): partners differing
+    by d = v_a - v_b, the cell's 32-bit Philox word, gq = round(gamma * 65536),
+    crq = round(cr * 65536).  0 unless (word >> 16) < crq, else floor((gq d + rr
+    + 0.5) / 65536) with rr = word & 0xFFFF."""
+    out = C.c_int(0)
+    if _lib.lib().mceik_de_delta(int(gq), int(d), int(word) & 0xFFFFFFFF, int(crq), C.byref(out)) != 0:
+        raise ValueError(f"de_delta: 1 <= gq <= {DE_GQ_MAX}, 1 <= crq <= {DE_CRQ_MAX}, delta within int32")
+    return out.value
+
+
+def de_draw(seed, gchain, step, nb):
+    """The step draw of a DE mover (mceik_de_draw; host only): (i, j, log u),
+    i != j the ordered pair of members of a partner set of nb >= 2."""
+    i, j, logu = C.c_int(0), C.c_int(0), C.c_double(0.0)
+    if _lib.lib().mceik_de_draw(int(seed), int(gchain), int(step), int(nb), C.byref(i), C.byref(j), C.byref(logu)) != 0:
+        raise ValueError("de_draw: nb >= 2")
+    return i.value, j.value, logu.value
+
+
+def de_movers(nchains, ntemps, k):
+    """DE step k of a sampler of `nchains` local chains in `ntemps` rungs (0 or
+    1: untempered): (movers, partners), movers the local chains that move, in
+    order, and partners[c] for each of them the partner set of its rung, in
+    order: the population of a chain is its rung, rung r holds
+    chains r * G + g, and g & 1 == k & 1 moves."""
+    nt = max(1, int(ntemps))
+    if nchains % nt:
+        raise ValueError("de_movers: nchains is a multiple of ntemps")
+    G, par = nchains // nt, int(k) & 1
+    movers = [c for c in range(nchains) if ((c % G) & 1) == par]
+    partners = {c: [(c // G) * G + g for g in range(G) if (g & 1) != par] for c in movers}
+    return movers, partners
+
+
 def nuis_ladder(nk, lam_min, lam_max):
     """(lam, lnlam) float64 [nk]: a log-uniform noise ladder from lam_min to
     lam_max for `Sampler.nuis_enable`, lnlam[k] = (k - nk // 2) * ln(lam_max) /
@@ -511,6 +549,9 @@ def _nuis_same(a, b):
     return set(a) == set(b) and all(eq(a[k], b[k]) for k in a)
 
 
+_DE_COUNTERS = ("attempts", "accepts", "outbox", "failed", "moved")
+
+
 class Sampler:
     """One GPU's chains (include/mceik.h handle)."""
 
@@ -553,6 +594,7 @@ class Sampler:
         #                                 checkpoint: added to the device counters (_move_stats)
         self._cov = None                # (probes [(kind, index)], within) while the sampler holds covariance sums
         self._lang = False              # Langevin moves were enabled at least once
+        self._de = None                 # (every, offset, gq, crq) while DE moves are enabled
         self._ess = None                # (nlevels, probes [(kind, index)]) while the sampler holds batch-means sums
         self._fit = None                # (tick, nbins, zmax, t0_ref) while the sampler holds data-fit sums
         self._fit_active = False        # ... and adds kept steps to them (fit_enable .. fit_disable)
@@ -605,7 +647,9 @@ class Sampler:
         accept flags (and the per-solve reference ierr if with_ierr).  After a step:
         [nchains, nstat, nev] / [nchains, nstat] of the model each proposal changed
         (`last_phase`); after init / restore with two models: [nchains, 2, nstat, nev]
-        / [nchains, 2, nstat]."""
+        / [nchains, 2, nstat].  After a DE step (`de_enable`) accept is 0 for the
+        standing chains, only the movers' rows are that step's, and `last_phase`
+        is the step's phase for every chain."""
         tt, it, acc, ie = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
         self._L.mceik_mcmc_last(self._h, C.byref(tt), C.byref(it), C.byref(acc), C.byref(ie))
         p = self.p
@@ -652,6 +696,8 @@ class Sampler:
         if self._block is not None:      # the radii decide what the chains propose; the counters ride along
             att, acc = self.block_stats()
             ck["block"] = {"rmin": self._block[0], "rmax": self._block[1], "attempts": att, "accepts": acc}
+        if self._de is not None:         # the options decide what the chains propose; the counters ride along
+            ck["de"] = dict(zip(("every", "offset", "gamma_q16", "cr_q16"), self._de), **self.de_stats())
         if self._prior is not None:      # the weights and the reference model decide what the chains sample
             ck["prior"] = {"w_smooth": self._prior[0], "w_damp": self._prior[1], "vref_sha256": self._prior[2]}
         if self._hypo is not None:       # the positions are chain state; the options decide what is proposed
@@ -685,6 +731,10 @@ class Sampler:
         bk = ck.get("block")             # likewise: a checkpoint without the entry restores anywhere
         if bk is not None and (self._block is None or (int(bk["rmin"]), int(bk["rmax"])) != self._block):
             raise ValueError("the checkpoint was taken with other block-proposal radii")
+        dk = ck.get("de")                # likewise
+        if dk is not None and (self._de is None or
+                               tuple(int(dk[k]) for k in ("every", "offset", "gamma_q16", "cr_q16")) != self._de):
+            raise ValueError("the checkpoint was taken with other DE-move options")
         pk = ck.get("prior")             # likewise
         if pk is not None and (self._prior is None or
                                (tuple(pk["w_smooth"]), tuple(pk["w_damp"]), pk["vref_sha256"]) != self._prior):
@@ -734,6 +784,9 @@ class Sampler:
             self._rebase_stats("temper", tk)
         if bk is not None:
             self._rebase_stats("block", bk)
+        if dk is not None:               # zero the library's counters; the checkpoint's ride on as the base
+            self.de_stats(reset=True)
+            self._stats_base["de"] = {k: int(dk[k]) for k in _DE_COUNTERS}
         if hk is not None:
             self._rebase_stats("hypo", hk)
             sm = np.ascontiguousarray(hk["sum"], dtype=np.int64)
@@ -982,6 +1035,93 @@ class Sampler:
                "status": np.zeros(nch, np.int32)}
         self._lang_held(self._L.mceik_mcmc_lang_last(self._h, *[a.ctypes.data_as(C.c_void_p) for a in out.values()]),
                         "mceik_mcmc_lang_last")
+        return out
+
+    # --- differential-evolution moves (include/mceik.h mceik_mcmc_de_*) ---
+    def de_enable(self, every, offset=0, gamma=None, cr=1.0):
+        """Turn differential-evolution (population) moves on: global step gs
+        with gs % every == offset (and neither a hypocentre, a nuisance nor a
+        Langevin step) proposes v + gamma (v_a - v_b) on one phase model of
+        half the chains of every population -- a chain's temperature rung on
+        this sampler -- from two chains a, b of the other half, which stands
+        still on that step; each cell takes part with probability `cr`
+        (DESIGN.md s.21).  The move is symmetric, costs one forward per moving
+        chain, and is rejected whole when a cell would leave the box.  gamma
+        and cr are rounded to units of 1 / 65536 (`de_options`).  gamma=None:
+        2.38 / sqrt(2 cr ncell), the usual DE-MC scale for the cr * ncell cells
+        that move, clipped to a representable value; how good that default is
+        for this posterior has not been measured.  A population needs 4
+        chains.  Every step is then one launch (`info()["multi_step"]` is
+        False until `de_disable`).  Resets the counters."""
+        cr = float(cr)
+        if not (0.0 < cr <= 1.0):
+            raise ValueError("de_enable: 0 < cr <= 1")
+        if gamma is None:
+            gamma = min(2.38 / np.sqrt(2.0 * cr * self.p.ncell), 2.0)
+        gamma = float(gamma)
+        if not (0.0 < gamma <= 2.0):
+            raise ValueError("de_enable: 0 < gamma <= 2")
+        gq = min(max(int(round(gamma * 65536.0)), 1), DE_GQ_MAX)
+        crq = min(max(int(round(cr * 65536.0)), 1), DE_CRQ_MAX)
+        o = _lib.DeOpts(int(every), int(offset), gq, crq)
+        rc = self._L.mceik_mcmc_de_enable(self._h, C.byref(o))
+        if rc != 0:
+            raise (ValueError if rc == 1 else RuntimeError)(
+                f"mceik_mcmc_de_enable failed ({rc}): every >= 1, 0 <= offset < every, and 4 chains per population "
+                "(temperature rung)")
+        self._de = (int(every), int(offset), gq, crq)
+        self._stats_base.pop("de", None)
+
+    def de_disable(self):
+        if self._L.mceik_mcmc_de_disable(self._h) != 0:
+            raise RuntimeError("mceik_mcmc_de_disable failed")
+        self._de = None
+        self._stats_base.pop("de", None)
+
+    def _de_held(self, rc, what):
+        if rc != 0:
+            raise RuntimeError(f"{what} failed ({rc}): DE moves were never enabled (Sampler.de_enable)")
+
+    def de_options(self):
+        """The options in force (every = 0 after `de_disable`): every, offset,
+        gamma_q16, cr_q16 and the gamma and cr they stand for."""
+        o = _lib.DeOpts()
+        self._de_held(self._L.mceik_mcmc_de_get(self._h, C.byref(o)), "mceik_mcmc_de_get")
+        return {"every": o.every, "offset": o.offset, "gamma_q16": o.gamma_q16, "cr_q16": o.cr_q16,
+                "gamma": o.gamma_q16 / 65536.0, "cr": o.cr_q16 / 65536.0}
+
+    def de_stats(self, reset=False):
+        """{"attempts", "accepts", "outbox", "failed", "moved"} over the chains:
+        DE moves tried, accepted, rejected because a cell left the box, failed
+        (a solve of the move did not converge), and cells that changed in the
+        accepted moves; plus those of a restored checkpoint (until a reset)."""
+        t = [C.c_longlong(0) for _ in range(5)]
+        self._de_held(self._L.mceik_mcmc_de_stats(self._h, *[C.byref(x) for x in t], int(reset)), "mceik_mcmc_de_stats")
+        out = dict(zip(_DE_COUNTERS, (int(x.value) for x in t)))
+        base = self._stats_base.get("de")
+        if base is not None:
+            out = {k: out[k] + base[k] for k in out}
+        if reset:
+            self._stats_base.pop("de", None)
+        return out
+
+    def de_last(self):
+        """The last DE step: {"mover" int32 [nchains] (1: the chain moved), "a",
+        "b" int32 [nchains] (the partners as local chains, -1 for standing
+        chains), "phase" (-1: none yet), "nmove" int32 [nchains] (cells that the
+        proposal changed), "inbox", "status" int32 [nchains] (1: failed),
+        "logl_prop" float64 [nchains] (logL where the move left the box or
+        failed, 0 for standing chains), "accept" uint8 [nchains]}.  After a DE
+        step `last()` reports accept = 0 for the standing chains and only the
+        movers' table rows are the step's; `last_phase()` is the step's phase
+        for every chain."""
+        nch = self.nchains
+        i32 = lambda: np.zeros(nch, np.int32)  # noqa: E731
+        out = {"mover": i32(), "a": i32(), "b": i32(), "phase": np.zeros(1, np.int32), "nmove": i32(), "inbox": i32(),
+               "status": i32(), "logl_prop": np.zeros(nch), "accept": np.zeros(nch, np.uint8)}
+        self._de_held(self._L.mceik_mcmc_de_last(self._h, *[a.ctypes.data_as(C.c_void_p) for a in out.values()]),
+                      "mceik_mcmc_de_last")
+        out["phase"] = int(out["phase"][0])
         return out
 
     # --- smoothness / reference-model prior (include/mceik.h mceik_mcmc_prior_*) ---

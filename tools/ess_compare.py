@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Which move pays: effective sample size per second of the plain single-cell
-sampler, of block proposals and of discrete Langevin moves on one problem, the
-same seed and the same wall-clock budget each: needs a GPU.
+sampler, of block proposals, of discrete Langevin moves and of
+differential-evolution moves on one problem, the same seed and the same
+wall-clock budget each: needs a GPU.
 
 Problem: tests/_adjoint.ps_problem (24 x 24 x 16, P+S, 144 cells per model), 8
 chains.  Per configuration: --burn steps of burn-in, then steps in chunks of
@@ -30,6 +31,7 @@ CONFIGS = {
     "single-cell": lambda smp: None,
     "block": lambda smp: smp.block_enable(),
     "langevin": lambda smp: smp.lang_enable(every=4, sigma=4),
+    "de": lambda smp: smp.de_enable(every=2),
 }
 
 
@@ -68,6 +70,7 @@ def main():
         top = max(l for l in range(args.nlevels) if (steps >> l) >= args.batches or l == 0)
         st = mcmc.ess_summary(smp, level=top)
         nacc = int(smp.state()[2].sum())
+        de = smp.de_stats() if smp._de is not None else None      # (burn-in included)
         smp.close()
         ess, tau = s.ess[np.isfinite(s.ess)], s.tau[np.isfinite(s.tau)]
         ess_t = st.ess[np.isfinite(st.ess)]
@@ -83,7 +86,7 @@ def main():
                           "top_level": top, "top_ess_median": round(float(np.median(ess_t)), 1),
                           "top_ess_min": round(float(ess_t.min()), 1),
                           "top_ess_median_per_s": round(float(np.median(ess_t)) / dt, 3),
-                          "top_ess_min_per_s": round(float(ess_t.min()) / dt, 3)}), flush=True)
+                          "top_ess_min_per_s": round(float(ess_t.min()) / dt, 3), "de": de}), flush=True)
         assert s.count == steps and s.nchains == args.chains
 
 
