@@ -1145,6 +1145,97 @@ int mceik_mcmc_de_last(mceik_mcmc *s, int *mover, int *a, int *b, int *phase, in
 int mceik_de_delta(int gq, int d, uint32_t word, int crq, int *delta);
 int mceik_de_draw(uint32_t seed, uint32_t gchain, uint64_t step, int nb, int *i, int *j, double *logu);
 
+/* ---------------------------------------------------------------------------
+ * Transdimensional Voronoi-cell models (no reference
+ * counterpart).  Off by default.  While on, each phase model of each chain is a
+ * list of k nuclei (inversion cell, int velocity), kmin <= k <= kmax <=
+ * MCEIK_VOR_KMAX (512), in distinct cells, and the chain's cell model v is
+ * their raster:
+ *   v[cell] = the value of the nucleus minimising d2 = (mx dx)^2 + (my dy)^2 +
+ *             (mz dz)^2 (differences of cell indices per axis; metric = (mx,
+ *             my, mz)), ties to the nucleus in the smaller cell.
+ * List order is state (a birth appends, a death of slot j moves the last slot
+ * into j) but never changes v.  Every step that would propose a single cell is
+ * a Voronoi step instead; hypocentre and nuisance steps and swap rounds run as
+ * before (a swap exchanges the nuclei with the models).  Voronoi step n (n
+ * counts such steps below the global step under the options in force) works on
+ * phase n % nphase.  Global chain g at global step gs draws Philox4x32-10, key
+ * {g, seed}, counters {gs lo, gs hi, 6, 0} -> a0..a3 and {gs lo, gs hi, 6, 1}
+ * -> b0..b3; idx(r, n) = floor(r n / 2^32):
+ *   type = a0 >> 30   0 value: nucleus j = idx(a1, k) moves by delta = +-(1 +
+ *                       idx(a2, dv)), minus iff a0 & 1; leaving the box rejects
+ *                     1 move: nucleus j moves by (idx(a2, 2 dmax_x + 1) - dmax_x,
+ *                       idx(b0, ..y..) - dmax_y, idx(b1, ..z..) - dmax_z) cells;
+ *                       a zero displacement, a target outside the grid and a
+ *                       target cell that holds a nucleus each reject
+ *                     2 birth: k == kmax rejects; else a nucleus in the
+ *                       idx(a1, ncell - k)-th free cell, ascending, with value
+ *                       vlo + idx(a2, vhi - vlo + 1) (a draw from the prior)
+ *                     3 death: k == kmin rejects; else nucleus j goes
+ *   log u = det_log((a3 + 0.5) / 2^32)
+ * The prior is uniform on k, on sets of k distinct cells and on values, so
+ * every Hastings factor cancels: accept iff the move was not rejected above and
+ * log u < beta (logL' - logL), logL' honouring moved hypocentres, noise scale
+ * and statics.  A rejected move still runs the step's forward.
+ *
+ * enable takes the caller's nuclei (cells, vals [nchains][nphase][kmax], counts
+ * [nchains][nphase]; validated) or, all three NULL, draws k0 distinct cells per
+ * chain and phase (nucleus i in free cell idx(r0, ncell - i) of counter {i,
+ * phase, 6, 0xFFFFFFFF}, key {g, seed}), each with the chain's current v of its
+ * cell; it then rasters every model and recomputes every logL with one full
+ * forward.  It returns 1 (with a message, nothing changed) on options out of
+ * range, a grid / metric whose largest d2 does not fit 31 bits, invalid nuclei,
+ * or while block proposals, the smoothness prior, Langevin moves or DE moves
+ * are on; those four refuse to be enabled while Voronoi-cell models are on.
+ * disable leaves v as it stands.  While on, every step is one launch of each
+ * kernel (mceik_mcmc_info.multi_step reports 0), and mceik_mcmc_restore's v
+ * must be the raster of the nuclei in force (set them first).  The other
+ * functions return 1 before the first enable.  Every function returns 0, 1 on
+ * invalid arguments or -1 on a device failure. */
+#define MCEIK_VOR_KMAX 512
+typedef struct mceik_vor_opts { int kmin, kmax, k0, dv; int dmax[3]; int metric[3]; } mceik_vor_opts;
+/* Turns the models on (or replaces options and nuclei); resets the counters. */
+int mceik_mcmc_vor_enable(mceik_mcmc *s, const mceik_vor_opts *o, const int *cells, const int *vals, const int *counts);
+int mceik_mcmc_vor_disable(mceik_mcmc *s);
+/* The options, *on, and the nuclei ([nchains][nphase][kmax], counts [nchains][nphase]).  Any may be NULL. */
+int mceik_mcmc_vor_get(mceik_mcmc *s, mceik_vor_opts *o, int *on, int *cells, int *vals, int *counts);
+/* Replaces the nuclei (validated: counts in range, distinct cells, values in
+ * the box; 1 and nothing changed otherwise), rasters them and, with recompute,
+ * recomputes every logL with one full forward. */
+int mceik_mcmc_vor_set(mceik_mcmc *s, const int *cells, const int *vals, const int *counts, int recompute);
+/* Queues the raster of every model from the nuclei in force on the sampler's
+ * stream (v, and both slowness rows; no synchronisation).  It changes nothing
+ * -- v is that raster already -- and exists to be timed (tools/vor_cost.py). */
+int mceik_mcmc_vor_rasterize(mceik_mcmc *s);
+/* counters [4][5] over the chains, by move type: attempts, accepts, rejections
+ * for reason 1, 2, 3 (value: 1 left the box; move: 1 zero displacement, 2
+ * outside the grid, 3 occupied; birth: 1 k == kmax; death: 1 k == kmin). */
+int mceik_mcmc_vor_stats(mceik_mcmc *s, long long *counters, int reset);
+/* The last Voronoi step: *phase (-1: none yet); rec [nchains][8] = type, reason
+ * (0: not rejected before the forward), j (birth: the new slot, -1 when
+ * rejected), cell, value of the changed nucleus as proposed (cell -1: outside
+ * the grid or no birth), k', 0, 0; the proposed nuclei [nchains][kmax] (the
+ * first k'; the current ones where rejected); vprop [nchains][ncell], their
+ * raster (the stepped phase's proposed model); log u, logL' (logL where
+ * rejected before the forward) and accept [nchains].  Any may be NULL. */
+int mceik_mcmc_vor_last(mceik_mcmc *s, int *phase, int *rec, int *pcells, int *pvals, int *vprop, double *logu,
+                        double *logl_prop, unsigned char *accept);
+/* Exact sums over the kept states' cold chains: *n states, hist [nphase][kmax +
+ * 1] states by k, dens [nphase][ncell] states with a nucleus in the cell.
+ * They merge by addition; _set loads them (checkpoints). */
+int mceik_mcmc_vor_moments(mceik_mcmc *s, long long *n, unsigned long long *hist, unsigned long long *dens);
+int mceik_mcmc_vor_moments_set(mceik_mcmc *s, long long n, const unsigned long long *hist, const unsigned long long *dens);
+/* Host only (no GPU call), the arithmetic the kernels run.  vor_raster: v [ncx
+ * ncy ncz] of k >= 1 nuclei; 1 on invalid arguments.  vor_free_cell: the f-th
+ * (from 0) cell in ascending order holding none of the k nuclei, f < ncell - k;
+ * -1 on invalid arguments.  vor_draw: out [8] = type, j, f, signed delta, the
+ * birth value, dx, dy, dz of global chain gchain at global step `step` for a
+ * model of k nuclei, and log u. */
+int mceik_vor_raster(int ncx, int ncy, int ncz, const int *metric, const int *cells, const int *vals, int k, int *v);
+int mceik_vor_free_cell(const int *cells, int k, int ncell, int f);
+int mceik_vor_draw(uint32_t seed, uint32_t gchain, uint64_t step, int k, int ncell, int dv, int vlo, int vhi,
+                   const int *dmax, int *out, double *logu);
+
 #ifdef __cplusplus
 }
 #endif

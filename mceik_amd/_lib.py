@@ -133,6 +133,12 @@ class NuisOpts(C.Structure):
                 ("lam", C.c_void_p), ("lnlam", C.c_void_p), ("norm", C.c_void_p)]
 
 
+class VorOpts(C.Structure):
+    """mceik_vor_opts (include/mceik.h)."""
+    _fields_ = [("kmin", C.c_int), ("kmax", C.c_int), ("k0", C.c_int), ("dv", C.c_int), ("dmax", C.c_int * 3),
+                ("metric", C.c_int * 3)]
+
+
 class DeOpts(C.Structure):
     """mceik_de_opts (include/mceik.h)."""
     _fields_ = [("every", C.c_int), ("offset", C.c_int), ("gamma_q16", C.c_int), ("cr_q16", C.c_int)]
@@ -240,6 +246,9 @@ EXPORTS = ("eikonal3d_serial_driver", "eikonal3d_serial_driver_sp", "eikonal3d_b
            "mceik_mcmc_lang_last", "mceik_det_exp", "mceik_lang_cell",
            "mceik_mcmc_de_enable", "mceik_mcmc_de_disable", "mceik_mcmc_de_get", "mceik_mcmc_de_stats",
            "mceik_mcmc_de_last", "mceik_de_delta", "mceik_de_draw",
+           "mceik_mcmc_vor_enable", "mceik_mcmc_vor_disable", "mceik_mcmc_vor_get", "mceik_mcmc_vor_set",
+           "mceik_mcmc_vor_rasterize", "mceik_mcmc_vor_stats", "mceik_mcmc_vor_last", "mceik_mcmc_vor_moments", "mceik_mcmc_vor_moments_set",
+           "mceik_vor_raster", "mceik_vor_free_cell", "mceik_vor_draw",
            "mceik_parms_defaults", "mceik_parms_set", "mceik_parms_read", "mceik_parms_args", "mceik_parms_write",
            "mceik_comm_available", "mceik_comm_unique_id", "mceik_comm_init", "mceik_comm_finalize", "mceik_mcmc_gather",
            "os_path_exists", "os_path_isdir", "os_path_isfile", "os_makedirs", "os_mkdir")
@@ -406,6 +415,31 @@ def lib():
     L.mceik_de_delta.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_int, pi]
     L.mceik_de_draw.restype = C.c_int
     L.mceik_de_draw.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, pi, pi, C.POINTER(C.c_double)]
+    L.mceik_mcmc_vor_enable.restype = C.c_int
+    L.mceik_mcmc_vor_enable.argtypes = [C.c_void_p, C.POINTER(VorOpts), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mceik_mcmc_vor_disable.restype = C.c_int
+    L.mceik_mcmc_vor_disable.argtypes = [C.c_void_p]
+    L.mceik_mcmc_vor_get.restype = C.c_int
+    L.mceik_mcmc_vor_get.argtypes = [C.c_void_p, C.POINTER(VorOpts), pi, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mceik_mcmc_vor_set.restype = C.c_int
+    L.mceik_mcmc_vor_set.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.mceik_mcmc_vor_rasterize.restype = C.c_int
+    L.mceik_mcmc_vor_rasterize.argtypes = [C.c_void_p]
+    L.mceik_mcmc_vor_stats.restype = C.c_int
+    L.mceik_mcmc_vor_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.mceik_mcmc_vor_last.restype = C.c_int
+    L.mceik_mcmc_vor_last.argtypes = [C.c_void_p] * 9
+    L.mceik_mcmc_vor_moments.restype = C.c_int
+    L.mceik_mcmc_vor_moments.argtypes = [C.c_void_p, C.POINTER(C.c_longlong), C.c_void_p, C.c_void_p]
+    L.mceik_mcmc_vor_moments_set.restype = C.c_int
+    L.mceik_mcmc_vor_moments_set.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]
+    L.mceik_vor_raster.restype = C.c_int
+    L.mceik_vor_raster.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.mceik_vor_free_cell.restype = C.c_int
+    L.mceik_vor_free_cell.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+    L.mceik_vor_draw.restype = C.c_int
+    L.mceik_vor_draw.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                 C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
     L.mceik_mcmc_prior_enable.restype = C.c_int
     L.mceik_mcmc_prior_enable.argtypes = [C.c_void_p, C.POINTER(PriorOpts)]
     L.mceik_mcmc_prior_disable.restype = C.c_int

@@ -19,12 +19,13 @@
 #include "nuis.h"
 #include "posterior.h"
 #include "prior.h"
+#include "vor.h"
 
 #define MCEIK_EV_RING 32           // hipEvent pairs around timed FSM launches (fixed ring)
 #define MCEIK_MAX_PIPES 4
 #define MCEIK_ITERS_N (6 + MCEIK_TRAFFIC_N)   // d_iters: iterations, 4 visit statistics, solves, traffic
 
-// A pipe: a part of the chains stepped on a stream of its own.  D, B, P, H, N, L, De, fb
+// A pipe: a part of the chains stepped on a stream of its own.  D, B, P, H, N, L, De, V, fb
 // and fb_hyp are views of the sampler's restricted to the pipe's chains;
 // pipes_refresh alone writes them.  (The accumulators of kept states --
 // posterior, covariances, batch means, data fit -- have no views: their
@@ -37,6 +38,7 @@ struct Pipe {
     NuisDev N;
     LangDev L;                         // (arrays null before the first lang_enable)
     DeDev De;                          // (arrays null before the first de_enable)
+    VorDev V;                          // (arrays null before the first vor_enable)
     mceik_fsm_batch fb;
     mceik_fsm_batch fb_hyp;            // a hypocentre step's batch (every model of the pipe's chains)
     void *ws;                          // the pipe's workspace: a part of the sampler's ws, ws itself, or its own
@@ -180,6 +182,16 @@ struct mceik_mcmc {
     int *d_demov;                      // [2][nchains]
     std::vector<int> de_mov[2];        // the host's copy
     int de_last_ph;                    // the last DE step's phase (-1: none yet)
+    // Voronoi-cell models (vor.hip); off by default.  V's arrays
+    // are null until the first enable.  While on, every chain's v is the raster
+    // of its nuclei, every step takes the per-step branch and every velocity
+    // step is a Voronoi step: vor.hip's kernels in place of propose / accept.
+    // plan_step says which phase a step works on.
+    bool vor_on;
+    int vor_k0;                        // the start count of the last enable (reported only)
+    VorDev V;
+    int vor_last_ph;                   // the last Voronoi step's phase (-1: none yet)
+    long long vor_n;                   // states in the moments (cold chains x kept steps)
     hipStream_t stream;
     void *ws;
     size_t ws_bytes;
@@ -217,12 +229,14 @@ int temper_round(mceik_mcmc *s, int parity);
 // fold sits between a step's proposal and its forward); hypocentre moves (a
 // hypocentre step has kernels and a batch of its own); held nuisance state (it
 // enters every logL, which the multi-step kernel's epilogue does not know);
-// Langevin moves and DE moves (such a step is a pipeline of launches of its own); the
+// Langevin moves and DE moves (such a step is a pipeline of launches of its own);
+// Voronoi-cell models (a velocity step rasters the proposed nuclei before its
+// forward, and the multi-step kernel's epilogue knows no nuclei); the
 // data-fit sums of a one-model sampler (they read the chains' current tables,
 // which the multi-step kernel's epilogue keeps for two models only).
 static inline bool mcmc_multi_step(const mceik_mcmc *s)
 {
-    return s->persist && !s->block_on && !s->prior_on && !s->hypo_on && !s->N.kn && !s->lang_on && !s->de_on &&
+    return s->persist && !s->block_on && !s->prior_on && !s->hypo_on && !s->N.kn && !s->lang_on && !s->de_on && !s->vor_on &&
            !(s->fit_on && s->D.nphase == 1);
 }
 // A one-model sampler's current tables (sampler_api.hip).  hold: while nuisance
@@ -240,6 +254,6 @@ size_t lang_pipe_bytes(const mceik_mcmc *s, int k, int m, size_t *u, size_t *fws
 // The DE mover lists for the populations in force (G = temper_cold); uploads
 // them and refreshes the pipes.  No-op before the first de_enable.  Synchronises.
 int de_lists(mceik_mcmc *s);
-// Recomputes every pipe's D, B, P, H, N, L, De and fb from the sampler's (and a multi-step
-// sampler's device copy of D): call after any change to s->D, s->B, s->P, s->H, s->N, s->L, s->De or s->fb.
+// Recomputes every pipe's D, B, P, H, N, L, De, V and fb from the sampler's (and a multi-step
+// sampler's device copy of D): call after any change to s->D, s->B, s->P, s->H, s->N, s->L, s->De, s->V or s->fb.
 int pipes_refresh(mceik_mcmc *s);

@@ -4,8 +4,8 @@
 //
 // Host orchestration only.  The numerics live in fsm_kernel.hip,
 // fsm16_kernel.hip, mcmc_kernels.hip, temper.hip, block.hip, prior.hip,
-// hypo.hip, nuis.hip, lang.hip, de.hip, adjoint.hip, posterior.hip, cov.hip,
-// ess.hip and fit.hip.
+// hypo.hip, nuis.hip, lang.hip, de.hip, vor.hip, adjoint.hip, posterior.hip,
+// cov.hip, ess.hip and fit.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -235,6 +235,20 @@ static DeDev dev_view(const DeDev &L, const McmcDev &D, const mceik_fsm_batch &f
     return V;
 }
 
+// The same view of the Voronoi state's per-chain arrays (the moments are the sampler's).
+static VorDev dev_view(const VorDev &L, const McmcDev &D, int off)
+{
+    VorDev V = L;
+    if (!L.cell) return V;
+    const size_t o = (size_t)off, on = o * D.nphase * L.kmax;
+    V.cell += on; V.val += on; V.cnt_k += o * D.nphase;
+    V.pcell += o * L.kmax; V.pval += o * L.kmax; V.pk += o;
+    V.rec += o * VOR_NREC; V.logl_prop += o;
+    V.vprop += o * D.ncell;
+    V.cnt += o * 4 * VOR_NCNT;
+    return V;
+}
+
 // Chains [off, off + n) of the hypocentre step's batch: nphase models per
 // chain.  It runs in the workspace of the pipe's step batch sb, so it keeps at
 // most that batch's resident waves (the workspace grows with the waves only).
@@ -286,6 +300,7 @@ int pipes_refresh(mceik_mcmc *s)
         p.N = dev_view(s->N, s->D, lo);
         p.L = dev_view(s->L, s->D, lo);
         p.De = dev_view(s->De, s->D, s->fb, s->de_mov, s->d_demov, lo, n);
+        p.V = dev_view(s->V, s->D, lo);
         if (s->H.hyp) p.fb_hyp = hyp_batch_view(s->fb_hyp, p.fb, lo, n, (size_t)s->D.ncm, s->D.nphase);
     }
     // the longest-first order covers the whole batch: one pipe's (mcmc_forward)
@@ -722,9 +737,11 @@ static long long next_kept_step(const mceik_mcmc *s)     // the first kept step 
 
 int temper_round(mceik_mcmc *s, int parity)
 {
-    // (per-chain hypocentres and nuisance state travel with their models, enabled or not)
+    // (per-chain hypocentres and nuisance state travel with their models, enabled or not; nuclei while they
+    // describe the models)
     HIPCHK(temper_swap_round(s->D, s->ntemps, parity, (uint64_t)s->step, s->d_tflag, s->d_tcnt,
-                             s->d_tcnt + s->D.nchains, s->stream, s->H.hyp ? &s->H : nullptr, s->N.kn ? &s->N : nullptr));
+                             s->d_tcnt + s->D.nchains, s->stream, s->H.hyp ? &s->H : nullptr, s->N.kn ? &s->N : nullptr,
+                             s->vor_on ? &s->V : nullptr));
     return 0;
 }
 
@@ -735,6 +752,9 @@ int temper_round(mceik_mcmc *s, int parity)
 // to step gs > 0 with gs % swap_every == 0 and runs before its proposal, with
 // parity (gs / swap_every) & 1.  DE step k = (gs - de_offset) / de_every moves
 // the chains of parity k & 1 of every population on phase (k >> 1) % nphase.
+// While Voronoi-cell models are on a velocity step is a Voronoi step: the n-th
+// such step (n counts the velocity steps below gs under the options in force)
+// works on phase n % nphase.
 enum StepKind { STEP_VELOCITY, STEP_HYPO, STEP_NUIS, STEP_LANG, STEP_DE };
 
 struct StepPlan {
@@ -743,7 +763,35 @@ struct StepPlan {
     int parity;
     bool kept;                         // kept_step(gs)
     int de_par, de_ph;                 // STEP_DE: the movers' parity and the phase
+    int vor_ph;                        // STEP_VELOCITY while Voronoi-cell models are on: the phase
 };
+
+// Steps g in [0, gs) with g % m == r (0 <= r < m).
+static long long count_mod(long long gs, long long m, long long r) { return gs > r ? (gs - r + m - 1) / m : 0; }
+
+// Velocity steps below gs while neither Langevin nor DE moves are on (Voronoi-
+// cell models refuse both): gs minus the hypocentre steps, minus the nuisance
+// steps that are not hypocentre steps too.
+static long long velocity_steps_below(const mceik_mcmc *s, long long gs)
+{
+    const bool hy = s->hypo_on && s->hypo_every > 0;
+    const bool nu = s->nuis_on && s->N.kn && s->nuis_every > 0;
+    long long n = gs;
+    if (hy) n -= count_mod(gs, s->hypo_every, s->hypo_every - 1);
+    if (nu) n -= count_mod(gs, s->nuis_every, s->nuis_offset);
+    if (hy && nu) {
+        // steps that are both: the first one x below the common period, then one per period
+        long long a = s->hypo_every, b = s->nuis_every;
+        while (b) { const long long t = a % b; a = b; b = t; }
+        const long long period = (long long)s->hypo_every / a * s->nuis_every;
+        for (long long x = s->hypo_every - 1; x < period; x += s->hypo_every)
+            if (x % s->nuis_every == s->nuis_offset) {
+                n += count_mod(gs, period, x);
+                break;
+            }
+    }
+    return n;
+}
 
 static StepPlan plan_step(const mceik_mcmc *s, long long gs)
 {
@@ -759,12 +807,13 @@ static StepPlan plan_step(const mceik_mcmc *s, long long gs)
     q.swap = s->ntemps > 1 && s->swap_every > 0 && gs > 0 && gs % s->swap_every == 0;
     q.parity = q.swap ? (int)((gs / s->swap_every) & 1) : 0;
     q.kept = kept_step(s, gs);
+    q.vor_ph = s->vor_on && q.kind == STEP_VELOCITY ? (int)(velocity_steps_below(s, gs) % s->D.nphase) : 0;
     return q;
 }
 
-// The kept-state hook.  Six consumers see the cold chains of a kept step:
+// The kept-state hook.  Seven consumers see the cold chains of a kept step:
 // posterior, hypocentre moments, nuisance moments, covariances, batch means,
-// data fit.
+// data fit, Voronoi moments.
 // kept_queue queues those that are on for the cold chains of pipe p's view on
 // stream st; kept_counted counts the state on the host once every pipe is
 // queued (mcmc_ess_k depends on that count alone, so every pipe reads the
@@ -780,6 +829,7 @@ static int kept_queue(mceik_mcmc *s, const Pipe &p, hipStream_t st)
     if (s->cov_on) HIPCHK(mcmc_cov_accumulate(s->cov, p.D, p.H, p.N, off, n, st));
     if (s->ess_on) HIPCHK(mcmc_ess_accumulate(s->ess, p.D, p.H, p.N, off, n, mcmc_ess_k(s->ess), st));
     if (s->fit_on) HIPCHK(mcmc_fit_accumulate(s->fit, p.D, p.H, p.N, off, n, st));
+    if (s->vor_on) HIPCHK(vor_moments(p.D, p.V, n, st));
     return 0;
 }
 
@@ -791,6 +841,7 @@ static void kept_counted(mceik_mcmc *s)
     if (s->cov_on) mcmc_cov_counted(s->cov);
     if (s->ess_on) mcmc_ess_counted(s->ess);
     if (s->fit_on) mcmc_fit_counted(s->fit);
+    if (s->vor_on) s->vor_n += temper_cold(s);
 }
 
 // Chains [off, off + m) of pipe p's step batch as a Langevin step runs them:
@@ -1032,6 +1083,13 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
                 if (de_step(s, k, q, slot)) return -1;
                 break;
             case STEP_VELOCITY:
+                if (s->vor_on) {    // one move of the nuclei of one phase model: the raster, one forward
+                    HIPCHK(vor_propose(p.D, p.V, step, q.vor_ph, st));
+                    if (mcmc_forward(s, true, k)) return -1;
+                    HIPCHK(vor_accept(p.D, p.V, p.N, q.vor_ph, slot, st));
+                    s->vor_last_ph = q.vor_ph;
+                    break;
+                }
                 HIPCHK(blk ? block_propose(p.D, p.B, step, st) : mcmc_propose(p.D, step, st));
                 if (s->prior_on) HIPCHK(prior_fold(p.D, p.B, p.P, blk, st));
                 if (mcmc_forward(s, true, k)) return -1;

@@ -1,7 +1,7 @@
 // sampler_api.hip -- the sampler's accessors of the C-ABI (include/mceik.h:
 // sync, state, checkpoint / restore, kept samples, info, FSM statistics) and
 // its parallel-tempering, block-proposal, prior, hypocentre, noise / statics,
-// Langevin and differential-evolution entry points.
+// Langevin, differential-evolution and Voronoi-cell entry points.
 // The sampler itself is sampler.hip.
 #include <hip/hip_runtime.h>
 #include <float.h>
@@ -20,6 +20,15 @@
 #include "host_util.h"
 #include "mcmc_host.h"
 #include "sampler.h"
+
+// Voronoi-cell models are on: the moves that change single cells of v are refused.
+static int vor_refuses(const mceik_mcmc *s, const char *who)
+{
+    if (!s->vor_on) return 0;
+    fprintf(stderr, "%s: Voronoi-cell models are on (mceik_mcmc_vor_enable): v is the raster of the nuclei, which this "
+                    "feature would not keep\n", who);
+    return 1;
+}
 
 // The posterior holds states: a change of what the chains sample is refused.
 static bool post_holds_states(const mceik_mcmc *s) { return s->post && mcmc_post_count(s->post) > 0; }
@@ -156,6 +165,7 @@ extern "C" int mceik_mcmc_temper_swap(mceik_mcmc *s, int parity)
 extern "C" int mceik_mcmc_block_enable(mceik_mcmc *s, const mceik_block_opts *o)
 {
     if (!s || !o || o->rmin < 0 || o->rmax < o->rmin || o->rmax > MCEIK_BLOCK_RMAX) return 1;
+    if (vor_refuses(s, "mceik_mcmc_block_enable")) return 1;
     DeviceScope dg(s->device);
     HIPCHK(hipStreamSynchronize(s->stream));
     const int nch = s->D.nchains, nr = MCEIK_BLOCK_RMAX + 1;
@@ -227,6 +237,7 @@ static bool prior_weight_ok(double w) { return w >= 0.0 && w <= DBL_MAX; }
 extern "C" int mceik_mcmc_prior_enable(mceik_mcmc *s, const mceik_prior_opts *o)
 {
     if (!s || !o) return 1;
+    if (vor_refuses(s, "mceik_mcmc_prior_enable")) return 1;
     const McmcDev &D = s->D;
     for (int ph = 0; ph < 2; ph++)
         if (!prior_weight_ok(o->w_smooth[ph]) || !prior_weight_ok(o->w_damp[ph])) return 1;
@@ -848,6 +859,7 @@ static void lang_pipes_free(mceik_mcmc *s)
 extern "C" int mceik_mcmc_lang_enable(mceik_mcmc *s, const mceik_lang_opts *o)
 {
     if (!s || !o) return 1;
+    if (vor_refuses(s, "mceik_mcmc_lang_enable")) return 1;
     if (o->every <= 0 || o->offset < 0 || o->offset >= o->every || !(o->sigma > 0.0 && o->sigma <= DBL_MAX) ||
         o->dmax < 1 || o->dmax > MCEIK_LANG_DMAX)
         return 1;
@@ -1025,6 +1037,7 @@ int de_lists(mceik_mcmc *s)
 extern "C" int mceik_mcmc_de_enable(mceik_mcmc *s, const mceik_de_opts *o)
 {
     if (!s || !o) return 1;
+    if (vor_refuses(s, "mceik_mcmc_de_enable")) return 1;
     if (o->every < 1 || o->offset < 0 || o->offset >= o->every) {
         fprintf(stderr, "mceik_mcmc_de_enable: every >= 1 and 0 <= offset < every\n");
         return 1;
@@ -1149,6 +1162,290 @@ extern "C" int mceik_de_draw(uint32_t seed, uint32_t gchain, uint64_t step, int 
     if (i) *i = a;
     if (j) *j = b;
     if (logu) *logu = hypo_det_log_host(((double)r3 + 0.5) * (1.0 / 4294967296.0));
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Voronoi-cell models (include/mceik.h mceik_mcmc_vor_*)
+
+// Nuclei lists [nchains][nphase][kmax] with counts [nchains][nphase]: counts in
+// [kmin, kmax], cells distinct and on the grid, values in the phase's box.
+static int vor_check(const mceik_mcmc *s, const char *who, int kmin, int kmax, const int *cells, const int *vals,
+                     const int *counts)
+{
+    const McmcDev &D = s->D;
+    std::vector<int> sorted;
+    for (int r = 0; r < D.nchains * D.nphase; r++) {
+        const int ph = r % D.nphase, k = counts[r];
+        const int lo = ph ? D.vsmin : D.vmin, hi = ph ? D.vsmax : D.vmax;
+        if (k < kmin || k > kmax) {
+            fprintf(stderr, "%s: chain %d phase %d has %d nuclei outside [%d, %d]\n", who, r / D.nphase, ph, k, kmin, kmax);
+            return 1;
+        }
+        const int *c = cells + (size_t)r * kmax, *w = vals + (size_t)r * kmax;
+        for (int j = 0; j < k; j++)
+            if (c[j] < 0 || c[j] >= D.ncell || w[j] < lo || w[j] > hi) {
+                fprintf(stderr, "%s: chain %d phase %d nucleus %d: cell %d outside [0, %d) or value %d outside [%d, %d]\n",
+                        who, r / D.nphase, ph, j, c[j], D.ncell, w[j], lo, hi);
+                return 1;
+            }
+        sorted.assign(c, c + k);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) {
+            fprintf(stderr, "%s: chain %d phase %d has two nuclei in one cell\n", who, r / D.nphase, ph);
+            return 1;
+        }
+    }
+    return 0;
+}
+
+// The nuclei to the device, every chain's v, slow_cur and slow_prop from their
+// raster and, with recompute, logL from one full forward.  Synchronises.
+static int vor_load(mceik_mcmc *s, const char *who, const int *cells, const int *vals, const int *counts, bool recompute)
+{
+    const McmcDev &D = s->D;
+    const VorDev &L = s->V;
+    const size_t nr = (size_t)D.nchains * D.nphase;
+    HIPCHK(hipMemcpy(L.cell, cells, nr * L.kmax * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(L.val, vals, nr * L.kmax * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(L.cnt_k, counts, nr * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(vor_raster(L, D.ncell, (int)nr, L.cell, L.val, L.cnt_k, D.v, (size_t)D.ncell, D.slow_cur, D.slow_prop,
+                      (size_t)D.ncell, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    if (recompute) return forward_logl(s, who);
+    return 0;
+}
+
+extern "C" int mceik_mcmc_vor_enable(mceik_mcmc *s, const mceik_vor_opts *o, const int *cells, const int *vals,
+                                     const int *counts)
+{
+    if (!s || !o) return 1;
+    const char *who = "mceik_mcmc_vor_enable";
+    const McmcDev &D = s->D;
+    if ((cells || vals || counts) && !(cells && vals && counts)) return 1;
+    if (o->kmin < 1 || o->kmax < o->kmin || o->kmax > MCEIK_VOR_KMAX || o->kmax > D.ncell || o->dv < 1 ||
+        (!cells && (o->k0 < o->kmin || o->k0 > o->kmax))) {
+        fprintf(stderr, "%s: 1 <= kmin <= k0 <= kmax <= min(%d, ncell) and dv >= 1\n", who, MCEIK_VOR_KMAX);
+        return 1;
+    }
+    for (int a = 0; a < 3; a++)
+        if (o->dmax[a] < 0 || o->dmax[a] > 32767 || o->metric[a] < 1 || o->metric[a] > 32767) {
+            fprintf(stderr, "%s: 0 <= dmax <= 32767 and 1 <= metric <= 32767 per axis\n", who);
+            return 1;
+        }
+    if (o->dmax[0] + o->dmax[1] + o->dmax[2] == 0) {
+        fprintf(stderr, "%s: dmax is zero on every axis: no nucleus could move\n", who);
+        return 1;
+    }
+    if (vor_d2max(s->B.ncx, s->B.ncy, s->B.ncz, o->metric[0], o->metric[1], o->metric[2]) < 0) {
+        fprintf(stderr, "%s: the largest squared distance of this grid under this metric does not fit 31 bits\n", who);
+        return 1;
+    }
+    if (s->block_on || s->prior_on || s->lang_on || s->de_on) {
+        fprintf(stderr, "%s: %s on: they change single cells of v, which would no longer be the raster of the nuclei\n",
+                who, s->block_on ? "block proposals are" : s->prior_on ? "the smoothness prior is" :
+                     s->lang_on ? "Langevin moves are" : "DE moves are");
+        return 1;
+    }
+    if (cells && vor_check(s, who, o->kmin, o->kmax, cells, vals, counts)) return 1;
+    if (post_holds_states(s)) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    const size_t nch = D.nchains, nr = nch * D.nphase, cap = MCEIK_VOR_KMAX;
+    if (!s->V.cell) {                  // every array or none: a failed enable leaves the sampler as it was
+        VorDev A;
+        memset(&A, 0, sizeof(A));
+        if (dalloc(s, &A.cell, nr * cap) || dalloc(s, &A.val, nr * cap) || dalloc(s, &A.cnt_k, nr) ||
+            dalloc(s, &A.pcell, nch * cap) || dalloc(s, &A.pval, nch * cap) || dalloc(s, &A.pk, nch) ||
+            dalloc(s, &A.rec, nch * VOR_NREC) || dalloc(s, &A.logl_prop, nch) || dalloc(s, &A.vprop, nch * D.ncell) ||
+            dalloc(s, &A.cnt, nch * 4 * VOR_NCNT) || dalloc(s, &A.hist, (size_t)D.nphase * (cap + 1)) ||
+            dalloc(s, &A.dens, (size_t)D.nphase * D.ncell))
+            return -1;
+        s->V = A;
+    }
+    // the start nuclei: the caller's, or k0 drawn per chain and phase, each at the chain's current v of its cell
+    std::vector<int> hc(nr * o->kmax, 0), hw(nr * o->kmax, 0), hk(nr, o->k0);
+    if (cells) {
+        memcpy(hc.data(), cells, hc.size() * sizeof(int));
+        memcpy(hw.data(), vals, hw.size() * sizeof(int));
+        memcpy(hk.data(), counts, hk.size() * sizeof(int));
+    } else {
+        std::vector<int> v(nch * D.ncm);
+        HIPCHK(hipMemcpy(v.data(), D.v, v.size() * sizeof(int), hipMemcpyDeviceToHost));
+        for (size_t r = 0; r < nr; r++) {
+            const uint32_t g = (uint32_t)(D.chain_offset + (int)(r / D.nphase));
+            int *c = hc.data() + r * o->kmax, *w = hw.data() + r * o->kmax;
+            for (int i = 0; i < o->k0; i++) {
+                uint32_t q[4];
+                vor_philox(D.seed, g, (uint32_t)i, (uint32_t)(r % D.nphase), 0xFFFFFFFFu, q);
+                c[i] = vor_free_cell(c, i, vor_idx(q[0], D.ncell - i));
+                w[i] = v[r * D.ncell + c[i]];
+            }
+        }
+    }
+    VorDev &L = s->V;
+    const bool resized = L.kmax != o->kmax;
+    L.kmin = o->kmin; L.kmax = o->kmax; L.dv = o->dv;
+    L.dmx = o->dmax[0]; L.dmy = o->dmax[1]; L.dmz = o->dmax[2];
+    L.mx = o->metric[0]; L.my = o->metric[1]; L.mz = o->metric[2];
+    L.ncx = s->B.ncx; L.ncy = s->B.ncy; L.ncz = s->B.ncz;
+    HIPCHK(hipMemset(L.cnt, 0, nch * 4 * VOR_NCNT * 8));
+    if (resized) {                     // the histogram's rows have another length: the moments start over
+        HIPCHK(hipMemset(L.hist, 0, (size_t)D.nphase * (cap + 1) * 8));
+        HIPCHK(hipMemset(L.dens, 0, (size_t)D.nphase * D.ncell * 8));
+        s->vor_n = 0;
+    }
+    s->vor_k0 = cells ? 0 : o->k0;
+    s->vor_last_ph = -1;
+    s->vor_on = true;
+    if (pipes_refresh(s)) return -1;
+    return vor_load(s, who, hc.data(), hw.data(), hk.data(), true);
+}
+
+extern "C" int mceik_mcmc_vor_disable(mceik_mcmc *s)
+{
+    if (!s) return 1;
+    if (!s->vor_on) return 0;
+    if (post_holds_states(s)) return 1;
+    s->vor_on = false;                 // host state only: v stays the last raster, an ordinary cell model
+    return 0;
+}
+
+extern "C" int mceik_mcmc_vor_get(mceik_mcmc *s, mceik_vor_opts *o, int *on, int *cells, int *vals, int *counts)
+{
+    if (!s || !s->V.cell) return 1;
+    const VorDev &L = s->V;
+    if (o) {
+        o->kmin = L.kmin; o->kmax = L.kmax; o->k0 = s->vor_k0; o->dv = L.dv;
+        o->dmax[0] = L.dmx; o->dmax[1] = L.dmy; o->dmax[2] = L.dmz;
+        o->metric[0] = L.mx; o->metric[1] = L.my; o->metric[2] = L.mz;
+    }
+    if (on) *on = s->vor_on ? 1 : 0;
+    if (!cells && !vals && !counts) return 0;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    const size_t nr = (size_t)s->D.nchains * s->D.nphase;
+    if (cells) HIPCHK(hipMemcpy(cells, L.cell, nr * L.kmax * sizeof(int), hipMemcpyDeviceToHost));
+    if (vals) HIPCHK(hipMemcpy(vals, L.val, nr * L.kmax * sizeof(int), hipMemcpyDeviceToHost));
+    if (counts) HIPCHK(hipMemcpy(counts, L.cnt_k, nr * sizeof(int), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int mceik_mcmc_vor_set(mceik_mcmc *s, const int *cells, const int *vals, const int *counts, int recompute)
+{
+    if (!s || !s->vor_on || !cells || !vals || !counts) return 1;
+    if (vor_check(s, "mceik_mcmc_vor_set", s->V.kmin, s->V.kmax, cells, vals, counts)) return 1;
+    if (post_holds_states(s)) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return vor_load(s, "mceik_mcmc_vor_set", cells, vals, counts, recompute != 0);
+}
+
+extern "C" int mceik_mcmc_vor_rasterize(mceik_mcmc *s)
+{
+    if (!s || !s->vor_on) return 1;
+    DeviceScope dg(s->device);
+    const McmcDev &D = s->D;
+    HIPCHK(vor_raster(s->V, D.ncell, D.nchains * D.nphase, s->V.cell, s->V.val, s->V.cnt_k, D.v, (size_t)D.ncell, D.slow_cur,
+                      D.slow_prop, (size_t)D.ncell, s->stream));
+    return 0;
+}
+
+extern "C" int mceik_mcmc_vor_stats(mceik_mcmc *s, long long *counters, int reset)
+{
+    if (!s || !s->V.cell) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    const size_t nch = s->D.nchains, n = 4 * VOR_NCNT;
+    std::vector<unsigned long long> cnt(nch * n);
+    HIPCHK(hipMemcpy(cnt.data(), s->V.cnt, cnt.size() * 8, hipMemcpyDeviceToHost));
+    for (size_t q = 0; q < n && counters; q++) {
+        long long t = 0;
+        for (size_t c = 0; c < nch; c++) t += (long long)cnt[c * n + q];
+        counters[q] = t;
+    }
+    if (reset) HIPCHK(hipMemset(s->V.cnt, 0, cnt.size() * 8));
+    return 0;
+}
+
+extern "C" int mceik_mcmc_vor_last(mceik_mcmc *s, int *phase, int *rec, int *pcells, int *pvals, int *vprop, double *logu,
+                                   double *logl_prop, unsigned char *accept)
+{
+    if (!s || !s->V.cell) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    const size_t nch = s->D.nchains;
+    const VorDev &L = s->V;
+    if (phase) *phase = s->vor_last_ph;
+    if (rec) HIPCHK(hipMemcpy(rec, L.rec, nch * VOR_NREC * sizeof(int), hipMemcpyDeviceToHost));
+    if (pcells) HIPCHK(hipMemcpy(pcells, L.pcell, nch * L.kmax * sizeof(int), hipMemcpyDeviceToHost));
+    if (pvals) HIPCHK(hipMemcpy(pvals, L.pval, nch * L.kmax * sizeof(int), hipMemcpyDeviceToHost));
+    if (vprop) HIPCHK(hipMemcpy(vprop, L.vprop, nch * s->D.ncell * sizeof(int), hipMemcpyDeviceToHost));
+    if (logu) HIPCHK(hipMemcpy(logu, s->D.prop_logu, nch * 8, hipMemcpyDeviceToHost));
+    if (logl_prop) HIPCHK(hipMemcpy(logl_prop, L.logl_prop, nch * 8, hipMemcpyDeviceToHost));
+    if (accept) HIPCHK(hipMemcpy(accept, s->D.accept, nch, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int mceik_mcmc_vor_moments(mceik_mcmc *s, long long *n, unsigned long long *hist, unsigned long long *dens)
+{
+    if (!s || !s->V.cell) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    if (n) *n = s->vor_n;
+    if (hist) HIPCHK(hipMemcpy(hist, s->V.hist, (size_t)s->D.nphase * (s->V.kmax + 1) * 8, hipMemcpyDeviceToHost));
+    if (dens) HIPCHK(hipMemcpy(dens, s->V.dens, (size_t)s->D.nphase * s->D.ncell * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int mceik_mcmc_vor_moments_set(mceik_mcmc *s, long long n, const unsigned long long *hist,
+                                          const unsigned long long *dens)
+{
+    if (!s || !s->V.cell || n < 0 || !hist || !dens) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    HIPCHK(hipMemcpy(s->V.hist, hist, (size_t)s->D.nphase * (s->V.kmax + 1) * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s->V.dens, dens, (size_t)s->D.nphase * s->D.ncell * 8, hipMemcpyHostToDevice));
+    s->vor_n = n;
+    return 0;
+}
+
+static int vor_grid_ok(int ncx, int ncy, int ncz)
+{
+    return ncx >= 1 && ncy >= 1 && ncz >= 1 && (long long)ncx * ncy * ncz <= INT_MAX;
+}
+
+extern "C" int mceik_vor_raster(int ncx, int ncy, int ncz, const int *metric, const int *cells, const int *vals, int k,
+                                int *v)
+{
+    if (!vor_grid_ok(ncx, ncy, ncz) || !metric || !cells || !vals || !v || k < 1) return 1;
+    if (metric[0] < 1 || metric[1] < 1 || metric[2] < 1 || metric[0] > 32767 || metric[1] > 32767 || metric[2] > 32767 ||
+        vor_d2max(ncx, ncy, ncz, metric[0], metric[1], metric[2]) < 0)
+        return 1;
+    for (int j = 0; j < k; j++)
+        if (cells[j] < 0 || cells[j] >= ncx * ncy * ncz) return 1;
+    vor_raster_host(ncx, ncy, ncz, metric[0], metric[1], metric[2], cells, vals, k, v);
+    return 0;
+}
+
+extern "C" int mceik_vor_free_cell(const int *cells, int k, int ncell, int f)
+{
+    if (k < 0 || (k > 0 && !cells) || ncell < 1 || f < 0 || f >= ncell - k) return -1;
+    for (int j = 0; j < k; j++)
+        if (cells[j] < 0 || cells[j] >= ncell) return -1;
+    return vor_free_cell(cells, k, f);
+}
+
+extern "C" int mceik_vor_draw(uint32_t seed, uint32_t gchain, uint64_t step, int k, int ncell, int dv, int vlo, int vhi,
+                              const int *dmax, int *out, double *logu)
+{
+    if (k < 1 || k > ncell || dv < 1 || vhi < vlo || !dmax || dmax[0] < 0 || dmax[1] < 0 || dmax[2] < 0) return 1;
+    const VorDraw d = vor_draw(seed, gchain, step, k, ncell, dv, vlo, vhi, dmax[0], dmax[1], dmax[2]);
+    if (out) {
+        out[0] = d.type; out[1] = d.j; out[2] = d.f; out[3] = d.minus ? -d.mag : d.mag; out[4] = d.wnew;
+        out[5] = d.dx; out[6] = d.dy; out[7] = d.dz;
+    }
+    if (logu) *logu = hypo_det_log_host(((double)d.u + 0.5) * (1.0 / 4294967296.0));
     return 0;
 }
 

@@ -7,6 +7,7 @@
 #include "hypo.h"
 #include "mcmc_common.h"
 #include "nuis.h"
+#include "vor.h"
 
 // One swap round of the whole sampler (D is the sampler's state, never a
 // pipe's view; D.beta set) on stream st: the decide kernel, then the exchange
@@ -17,7 +18,8 @@
 // accepts: [ntemps - 1] counters.  H (or null): the chains' hypocentres and
 // event lists, N (or null) their nuisance state (kn, kc and the effective
 // rows), exchanged with the models; the current tables wherever the sampler
-// keeps them (D.ttab_cur).  No host synchronisation.
+// keeps them (D.ttab_cur).  V (or null): the sampler's Voronoi state, whose
+// nuclei rows and counts are exchanged with the models.  No host synchronisation.
 hipError_t temper_swap_round(const McmcDev &D, int ntemps, int parity, uint64_t gs, int *flag,
                              unsigned long long *attempts, unsigned long long *accepts, hipStream_t st,
-                             const HypoDev *H = nullptr, const NuisDev *N = nullptr);
+                             const HypoDev *H = nullptr, const NuisDev *N = nullptr, const VorDev *V = nullptr);

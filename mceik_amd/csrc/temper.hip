@@ -125,7 +125,7 @@ __global__ __launch_bounds__(TEMPER_BLOCK) void temper_exchange_kernel(TemperRow
 
 hipError_t temper_swap_round(const McmcDev &D, int ntemps, int parity, uint64_t gs, int *flag,
                              unsigned long long *attempts, unsigned long long *accepts, hipStream_t st,
-                             const HypoDev *H, const NuisDev *N)
+                             const HypoDev *H, const NuisDev *N, const VorDev *V)
 {
     if (ntemps < 2 || !D.beta) return hipSuccess;
     const int G = D.nchains / ntemps, npairs = (ntemps - 1) * G;
@@ -165,6 +165,18 @@ hipError_t temper_swap_round(const McmcDev &D, int ntemps, int parity, uint64_t 
         Q.p0 = (unsigned *)N->kn; Q.p1 = (unsigned *)N->kc; Q.p2 = (unsigned *)N->var_eff; Q.p3 = (unsigned *)N->tcorr_eff;
         Q.len0 = D.nphase; Q.len1 = D.nphase * D.nstat; Q.len2 = Q.len3 = 2 * N->nobs;
         Q.t1 = tiles(Q.len0); Q.t2 = Q.t1 + tiles(Q.len1); Q.t3 = Q.t2 + tiles(Q.len2); Q.t4 = Q.t3 + tiles(Q.len3);
+        for (int p0 = 0; p0 < npairs; p0 += TEMPER_MAX_GRID_Y) {
+            const int np = npairs - p0 < TEMPER_MAX_GRID_Y ? npairs - p0 : TEMPER_MAX_GRID_Y;
+            hipLaunchKernelGGL(temper_exchange_kernel, dim3(Q.t4, np), dim3(TEMPER_BLOCK), 0, st, Q, flag, p0, G);
+        }
+    }
+    if (V && V->cell) {
+        // the nuclei and their counts (vor.h): rows of nphase * kmax ints twice and of nphase ints
+        auto tiles = [](int len) { return (len + TEMPER_TILE - 1) / TEMPER_TILE; };
+        TemperRows Q;
+        Q.p0 = (unsigned *)V->cell; Q.p1 = (unsigned *)V->val; Q.p2 = (unsigned *)V->cnt_k; Q.p3 = nullptr;
+        Q.len0 = Q.len1 = D.nphase * V->kmax; Q.len2 = D.nphase; Q.len3 = 0;
+        Q.t1 = tiles(Q.len0); Q.t2 = Q.t1 + tiles(Q.len1); Q.t3 = Q.t2 + tiles(Q.len2); Q.t4 = Q.t3;
         for (int p0 = 0; p0 < npairs; p0 += TEMPER_MAX_GRID_Y) {
             const int np = npairs - p0 < TEMPER_MAX_GRID_Y ? npairs - p0 : TEMPER_MAX_GRID_Y;
             hipLaunchKernelGGL(temper_exchange_kernel, dim3(Q.t4, np), dim3(TEMPER_BLOCK), 0, st, Q, flag, p0, G);

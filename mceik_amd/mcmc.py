@@ -474,6 +474,56 @@ def de_movers(nchains, ntemps, k):
     return movers, partners
 
 
+VOR_KMAX = 512
+VOR_TYPES = ("value", "move", "birth", "death")
+VOR_COUNTERS = ("attempts", "accepts", "reason1", "reason2", "reason3")
+
+
+def _i32(a):
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def vor_raster(grid, cells, vals, metric=(1, 1, 1)):
+    """The raster of Voronoi nuclei (mceik_vor_raster; host only): int32 [ncell]
+    of the grid (a Problem, or (ncx, ncy, ncz)), v[cell] the value of the
+    nucleus minimising (mx dx)^2 + (my dy)^2 + (mz dz)^2 in cell-index units,
+    ties to the nucleus in the smaller cell."""
+    ncx, ncy, ncz = (grid.ncx, grid.ncy, grid.ncz) if hasattr(grid, "ncx") else (int(x) for x in grid)
+    c, w, m = _i32(cells).ravel(), _i32(vals).ravel(), _i32(metric).ravel()
+    if c.size != w.size or m.size != 3:
+        raise ValueError("vor_raster: as many values as cells, and a metric of three")
+    v = np.empty(max(ncx * ncy * ncz, 1), np.int32)
+    if _lib.lib().mceik_vor_raster(ncx, ncy, ncz, m.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p),
+                                   w.ctypes.data_as(C.c_void_p), int(c.size), v.ctypes.data_as(C.c_void_p)) != 0:
+        raise ValueError("vor_raster: at least one nucleus, cells on the grid, a positive metric whose largest "
+                         "squared distance fits 31 bits")
+    return v
+
+
+def vor_free_cell(cells, ncell, f):
+    """The f-th (from 0) cell of [0, ncell) in ascending order that holds none
+    of the nuclei `cells` (mceik_vor_free_cell; host only)."""
+    c = _i32(cells).ravel()
+    r = _lib.lib().mceik_vor_free_cell(c.ctypes.data_as(C.c_void_p), int(c.size), int(ncell), int(f))
+    if r < 0:
+        raise ValueError("vor_free_cell: cells in [0, ncell) and 0 <= f < ncell - k")
+    return r
+
+
+def vor_draw(seed, gchain, step, k, ncell, dv, vlo, vhi, dmax=(1, 1, 1)):
+    """The draw of a Voronoi step (mceik_vor_draw; host only) for a phase model
+    of k nuclei: {"type" (0 value, 1 move, 2 birth, 3 death), "j", "f", "delta",
+    "wnew", "d" (dx, dy, dz), "logu"} -- each move type reads its own fields
+    (DESIGN.md s.22)."""
+    out, logu, dm = np.zeros(8, np.int32), C.c_double(0.0), _i32(dmax).ravel()
+    if dm.size != 3 or _lib.lib().mceik_vor_draw(int(seed), int(gchain), int(step), int(k), int(ncell), int(dv), int(vlo),
+                                                 int(vhi), dm.ctypes.data_as(C.c_void_p),
+                                                 out.ctypes.data_as(C.c_void_p), C.byref(logu)) != 0:
+        raise ValueError("vor_draw: 1 <= k <= ncell, dv >= 1, vlo <= vhi, dmax >= 0 per axis")
+    return {"type": int(out[0]), "j": int(out[1]), "f": int(out[2]), "delta": int(out[3]), "wnew": int(out[4]),
+            "d": (int(out[5]), int(out[6]), int(out[7])), "logu": logu.value}
+
+
 def nuis_ladder(nk, lam_min, lam_max):
     """(lam, lnlam) float64 [nk]: a log-uniform noise ladder from lam_min to
     lam_max for `Sampler.nuis_enable`, lnlam[k] = (k - nk // 2) * ln(lam_max) /
@@ -595,6 +645,7 @@ class Sampler:
         self._cov = None                # (probes [(kind, index)], within) while the sampler holds covariance sums
         self._lang = False              # Langevin moves were enabled at least once
         self._de = None                 # (every, offset, gq, crq) while DE moves are enabled
+        self._vor = None                # (kmin, kmax, dv, dmax, metric) while Voronoi-cell models are enabled
         self._ess = None                # (nlevels, probes [(kind, index)]) while the sampler holds batch-means sums
         self._fit = None                # (tick, nbins, zmax, t0_ref) while the sampler holds data-fit sums
         self._fit_active = False        # ... and adds kept steps to them (fit_enable .. fit_disable)
@@ -698,6 +749,10 @@ class Sampler:
             ck["block"] = {"rmin": self._block[0], "rmax": self._block[1], "attempts": att, "accepts": acc}
         if self._de is not None:         # the options decide what the chains propose; the counters ride along
             ck["de"] = dict(zip(("every", "offset", "gamma_q16", "cr_q16"), self._de), **self.de_stats())
+        if self._vor is not None:        # the nuclei are chain state; the options decide what is proposed
+            cells, vals, counts = self.vor_get()
+            ck["vor"] = {"opts": self.vor_options(), "cells": cells, "vals": vals, "counts": counts,
+                         "stats": self.vor_stats(), "moments": self.vor_moments()}
         if self._prior is not None:      # the weights and the reference model decide what the chains sample
             ck["prior"] = {"w_smooth": self._prior[0], "w_damp": self._prior[1], "vref_sha256": self._prior[2]}
         if self._hypo is not None:       # the positions are chain state; the options decide what is proposed
@@ -735,6 +790,15 @@ class Sampler:
         if dk is not None and (self._de is None or
                                tuple(int(dk[k]) for k in ("every", "offset", "gamma_q16", "cr_q16")) != self._de):
             raise ValueError("the checkpoint was taken with other DE-move options")
+        vk = ck.get("vor")               # the nuclei describe v: a sampler with the models on wants them
+        if vk is None and self._vor is not None:
+            raise ValueError("Voronoi-cell models are on and the checkpoint carries no nuclei")
+        if vk is not None:
+            o = vk["opts"]
+            if self._vor is None or (int(o["kmin"]), int(o["kmax"]), int(o["dv"]), tuple(int(x) for x in o["dmax"]),
+                                     tuple(int(x) for x in o["metric"])) != self._vor:
+                raise ValueError("the checkpoint was taken with other Voronoi-cell options")
+            self.vor_set(vk["cells"], vk["vals"], vk["counts"], recompute_logl=False)   # (the restore below sets logL)
         pk = ck.get("prior")             # likewise
         if pk is not None and (self._prior is None or
                                (tuple(pk["w_smooth"]), tuple(pk["w_damp"]), pk["vref_sha256"]) != self._prior):
@@ -787,6 +851,10 @@ class Sampler:
         if dk is not None:               # zero the library's counters; the checkpoint's ride on as the base
             self.de_stats(reset=True)
             self._stats_base["de"] = {k: int(dk[k]) for k in _DE_COUNTERS}
+        if vk is not None:               # zero the library's counters; the checkpoint's ride on as the base
+            self.vor_stats(reset=True)
+            self._stats_base["vor"] = {t: dict(vk["stats"][t]) for t in VOR_TYPES}
+            self.vor_moments_set(vk["moments"])
         if hk is not None:
             self._rebase_stats("hypo", hk)
             sm = np.ascontiguousarray(hk["sum"], dtype=np.int64)
@@ -1123,6 +1191,171 @@ class Sampler:
                       "mceik_mcmc_de_last")
         out["phase"] = int(out["phase"][0])
         return out
+
+    # --- transdimensional Voronoi-cell models (include/mceik.h mceik_mcmc_vor_*) ---
+    def _vor_nuclei(self, cells, vals, counts, kmax):
+        shape = (self.nchains, max(1, self.p.nphase), kmax)
+        c, w, k = _i32(cells), _i32(vals), _i32(counts)
+        if c.size != np.prod(shape) or w.size != c.size or k.size != shape[0] * shape[1]:
+            raise ValueError(f"nuclei: cells and vals {shape}, counts {shape[:2]}")
+        return c.reshape(shape), w.reshape(shape), k.reshape(shape[:2])
+
+    def vor_enable(self, kmin=1, kmax=64, k0=None, dv=None, dmax=(1, 1, 1), metric=(1, 1, 1), nuclei=None):
+        """Turn transdimensional Voronoi-cell models on: each phase model of
+        each chain becomes kmin <= k <= kmax (<= VOR_KMAX) nuclei (cell, value)
+        in distinct cells, v is their raster (`vor_raster`), and every step that
+        would propose a single cell draws one of four moves of one phase's
+        nuclei instead -- value (+-[1, dv], default the problem's dvmax), move
+        (up to dmax cells per axis), birth (a free cell, its value from the
+        prior), death -- accepted iff log u < beta (logL' - logL): with a
+        uniform prior on k, on the cells and on the values no Hastings factor
+        remains.  nuclei = (cells, vals [nchains, nphase,
+        kmax], counts [nchains, nphase]) starts from the caller's; otherwise k0
+        (default kmin) distinct cells are drawn per chain and phase, each with
+        the chain's current v of its cell.  The models are rastered and every
+        logL recomputed with one forward.  Refused while block proposals, the
+        smoothness prior, Langevin or DE moves are on, which in turn refuse
+        while this is on.  Every step is then one launch
+        (`info()["multi_step"]` is False until `vor_disable`).  Resets the
+        counters."""
+        o = _lib.VorOpts()
+        o.kmin, o.kmax, o.dv = int(kmin), int(kmax), int(self.p.dvmax if dv is None else dv)
+        o.k0 = int(kmin if k0 is None else k0)
+        dm, me = tuple(int(x) for x in dmax), tuple(int(x) for x in metric)
+        if len(dm) != 3 or len(me) != 3:
+            raise ValueError("vor_enable: dmax and metric have three entries")
+        o.dmax[:], o.metric[:] = dm, me
+        ptr = [None, None, None]
+        if nuclei is not None:
+            if not 1 <= o.kmax <= VOR_KMAX:
+                raise ValueError(f"vor_enable: 1 <= kmax <= {VOR_KMAX}")
+            keep = self._vor_nuclei(*nuclei, o.kmax)
+            ptr = [a.ctypes.data_as(C.c_void_p) for a in keep]
+        rc = self._L.mceik_mcmc_vor_enable(self._h, C.byref(o), *ptr)
+        if rc != 0:
+            raise (ValueError if rc == 1 else RuntimeError)(
+                f"mceik_mcmc_vor_enable failed ({rc}): 1 <= kmin <= k0 <= kmax <= min({VOR_KMAX}, ncell), dv >= 1, valid "
+                "nuclei, and neither block proposals, the prior, Langevin nor DE moves on")
+        self._vor = (o.kmin, o.kmax, o.dv, dm, me)
+        self._stats_base.pop("vor", None)
+        self._last_full = True
+
+    def vor_disable(self):
+        """Later steps propose single cells again, from v as it stands."""
+        if self._L.mceik_mcmc_vor_disable(self._h) != 0:
+            raise RuntimeError("mceik_mcmc_vor_disable failed")
+        self._vor = None
+        self._stats_base.pop("vor", None)
+
+    def _vor_held(self, rc, what):
+        if rc != 0:
+            raise RuntimeError(f"{what} failed ({rc}): Voronoi-cell models were never enabled (Sampler.vor_enable)")
+
+    def vor_options(self):
+        """The options in force: kmin, kmax, k0 (0 when the caller gave the nuclei), dv, dmax, metric, on."""
+        o, on = _lib.VorOpts(), C.c_int(0)
+        self._vor_held(self._L.mceik_mcmc_vor_get(self._h, C.byref(o), C.byref(on), None, None, None), "mceik_mcmc_vor_get")
+        return {"kmin": o.kmin, "kmax": o.kmax, "k0": o.k0, "dv": o.dv, "dmax": tuple(o.dmax), "metric": tuple(o.metric),
+                "on": bool(on.value)}
+
+    def vor_get(self):
+        """(cells, vals int32 [nchains, nphase, kmax], counts int32 [nchains,
+        nphase]): the nuclei; slots from a model's count on mean nothing."""
+        kmax = self.vor_options()["kmax"]
+        shape = (self.nchains, max(1, self.p.nphase), kmax)
+        c, w, k = np.zeros(shape, np.int32), np.zeros(shape, np.int32), np.zeros(shape[:2], np.int32)
+        self._vor_held(self._L.mceik_mcmc_vor_get(self._h, None, None, *[a.ctypes.data_as(C.c_void_p) for a in (c, w, k)]),
+                       "mceik_mcmc_vor_get")
+        return c, w, k
+
+    def vor_set(self, cells, vals, counts, recompute_logl=True):
+        """Replace the nuclei (validated: counts in [kmin, kmax], distinct cells,
+        values in the box), raster them and recompute every logL."""
+        if self._vor is None:
+            raise RuntimeError("vor_set: Voronoi-cell models are off")
+        keep = self._vor_nuclei(cells, vals, counts, self._vor[1])
+        rc = self._L.mceik_mcmc_vor_set(self._h, *[a.ctypes.data_as(C.c_void_p) for a in keep], int(bool(recompute_logl)))
+        if rc != 0:
+            raise (ValueError if rc == 1 else RuntimeError)(f"mceik_mcmc_vor_set failed ({rc}): invalid nuclei")
+        if recompute_logl:
+            self._last_full = True
+
+    def vor_rasterize(self):
+        """Queue the raster of every model from its nuclei on the sampler's
+        stream, without a synchronise (mceik_mcmc_vor_rasterize).  v is that
+        raster already: this is for timing the kernel (tools/vor_cost.py)."""
+        if self._L.mceik_mcmc_vor_rasterize(self._h) != 0:
+            raise RuntimeError("mceik_mcmc_vor_rasterize failed: Voronoi-cell models are off")
+
+    def vor_stats(self, reset=False):
+        """{move type: {"attempts", "accepts", "reason1", "reason2", "reason3"}}
+        over the chains; the reasons count moves rejected before their forward
+        -- value: 1 left the box; move: 1 zero displacement, 2 outside the grid,
+        3 occupied; birth: 1 k == kmax; death: 1 k == kmin -- plus those of a
+        restored checkpoint (until a reset)."""
+        t = np.zeros((4, 5), np.int64)
+        self._vor_held(self._L.mceik_mcmc_vor_stats(self._h, t.ctypes.data_as(C.c_void_p), int(reset)),
+                       "mceik_mcmc_vor_stats")
+        out = {n: dict(zip(VOR_COUNTERS, (int(x) for x in t[i]))) for i, n in enumerate(VOR_TYPES)}
+        base = self._stats_base.get("vor")
+        if base is not None:
+            out = {n: {k: out[n][k] + int(base[n][k]) for k in VOR_COUNTERS} for n in VOR_TYPES}
+        if reset:
+            self._stats_base.pop("vor", None)
+        return out
+
+    def vor_last(self):
+        """The last Voronoi step: {"phase" (-1: none yet), "type", "reason" (0:
+        not rejected before the forward), "j", "cell", "value" (the changed
+        nucleus as proposed), "k" (the proposed count) int32 [nchains],
+        "cells", "vals" int32 [nchains, kmax] (the proposed nuclei: the first
+        k), "vprop" int32 [nchains, ncell] (their raster), "logu", "logl_prop" float64 [nchains] (logL where rejected before
+        the forward), "accept" uint8 [nchains]}."""
+        nch, kmax = self.nchains, self.vor_options()["kmax"]
+        ph, rec = C.c_int(-1), np.zeros((nch, 8), np.int32)
+        pc, pw = np.zeros((nch, kmax), np.int32), np.zeros((nch, kmax), np.int32)
+        vp = np.zeros((nch, self.p.ncell), np.int32)
+        lu, lp, acc = np.zeros(nch), np.zeros(nch), np.zeros(nch, np.uint8)
+        self._vor_held(self._L.mceik_mcmc_vor_last(self._h, C.byref(ph), *[a.ctypes.data_as(C.c_void_p)
+                                                                          for a in (rec, pc, pw, vp, lu, lp, acc)]),
+                       "mceik_mcmc_vor_last")
+        out = {"phase": ph.value}
+        for i, n in enumerate(("type", "reason", "j", "cell", "value", "k")):
+            out[n] = rec[:, i].copy()
+        out.update(cells=pc, vals=pw, vprop=vp, logu=lu, logl_prop=lp, accept=acc)
+        return out
+
+    def vor_moments(self):
+        """{"n", "hist" uint64 [nphase, kmax + 1], "dens" uint64 [nphase,
+        ncell]}: exact sums over the cold chains of the kept steps -- states by
+        k, and states with a nucleus in each cell.  They merge by addition."""
+        nph, kmax = max(1, self.p.nphase), self.vor_options()["kmax"]
+        n, hist, dens = C.c_longlong(0), np.zeros((nph, kmax + 1), np.uint64), np.zeros((nph, self.p.ncell), np.uint64)
+        self._vor_held(self._L.mceik_mcmc_vor_moments(self._h, C.byref(n), hist.ctypes.data_as(C.c_void_p),
+                                                      dens.ctypes.data_as(C.c_void_p)), "mceik_mcmc_vor_moments")
+        return {"n": int(n.value), "hist": hist, "dens": dens}
+
+    def vor_moments_set(self, m):
+        hist = np.ascontiguousarray(m["hist"], dtype=np.uint64)
+        dens = np.ascontiguousarray(m["dens"], dtype=np.uint64)
+        nph, kmax = max(1, self.p.nphase), self.vor_options()["kmax"]
+        if hist.shape != (nph, kmax + 1) or dens.shape != (nph, self.p.ncell):
+            raise ValueError("vor_moments_set: hist [nphase, kmax + 1], dens [nphase, ncell]")
+        self._vor_held(self._L.mceik_mcmc_vor_moments_set(self._h, int(m["n"]), hist.ctypes.data_as(C.c_void_p),
+                                                          dens.ctypes.data_as(C.c_void_p)), "mceik_mcmc_vor_moments_set")
+
+    def vor_summary(self, moments=None):
+        """{"n", "k_posterior" float64 [nphase, kmax + 1] (the kept states'
+        share by k), "k_mean" [nphase], "acceptance" {move type: accepts /
+        attempts}, "density" float64 [nphase, ncell] (the share of kept states
+        with a nucleus in the cell)} from `vor_moments()` (or merged ones)."""
+        m = self.vor_moments() if moments is None else moments
+        n = max(int(m["n"]), 1)
+        kp = np.asarray(m["hist"], np.float64) / n
+        st = self.vor_stats()
+        return {"n": int(m["n"]), "k_posterior": kp, "k_mean": kp @ np.arange(kp.shape[1], dtype=np.float64),
+                "acceptance": {t: st[t]["accepts"] / max(st[t]["attempts"], 1) for t in VOR_TYPES},
+                "density": np.asarray(m["dens"], np.float64) / n}
 
     # --- smoothness / reference-model prior (include/mceik.h mceik_mcmc_prior_*) ---
     def prior_enable(self, sigma_smooth=None, sigma_damp=None, vref=None):
