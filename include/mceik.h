@@ -1236,6 +1236,35 @@ int mceik_vor_free_cell(const int *cells, int k, int ncell, int f);
 int mceik_vor_draw(uint32_t seed, uint32_t gchain, uint64_t step, int k, int ncell, int dv, int vlo, int vhi,
                    const int *dmax, int *out, double *logu);
 
+/* ---- the likelihood's norm (csrc/l1.h) ------------------
+ * norm = 2 (default): the weighted L2 misfit with the analytic origin time.
+ * norm = 1: a Laplace density of scale var_j per pick, the origin time of an
+ * event its lower weighted median.  For the used picks j of event e in
+ * catalogue order, x_j = (tobs_j - tcorr_j) - te_j and w_j = 1 / var_j:
+ *   W = sum_j w_j;  s_k = sum_j ((x_j < x_k || (x_j == x_k && j <= k)) ? w_j : 0)
+ *   t0 = the smallest x_k with s_k >= 0.5 W;  objfn_e = sum_j w_j |x_j - t0|
+ * (every sum in ascending j; no used pick: 0) and logL = -sum_e objfn_e, plus
+ * the noise-ladder term of held nuisance state as under L2.  The norm is a
+ * property of the sampler: the single-cell, block, DE and Voronoi accepts,
+ * hypocentre and nuisance moves, tempering swaps and the data-fit stream (whose
+ * origin time becomes the median) all follow it.  While norm = 1 every step is
+ * one launch of each kernel (mceik_mcmc_info.multi_step reports 0).
+ *
+ * set recomputes every chain's logL under the new norm with one full forward;
+ * the step counter and the models are untouched.  It returns 1, with nothing
+ * changed, for a norm other than 1 or 2, while Langevin moves are on, or while
+ * an enabled accumulator of kept states (posterior, covariances, batch means,
+ * data fit, the hypocentre / nuisance / Voronoi moments) already holds states;
+ * 2 when a solve of the forward failed; -1 on a device failure.
+ * mceik_mcmc_lang_enable is refused while norm = 1.  get returns 1 or 2 (0:
+ * null handle).  A checkpoint does not carry the norm: the caller restores
+ * into a sampler of the same norm (mceik_amd.mcmc.Sampler does). */
+int mceik_mcmc_likelihood_set(mceik_mcmc *s, int norm);
+int mceik_mcmc_likelihood_get(const mceik_mcmc *s);
+/* Host only (no GPU call): the event objective above on n residuals x with
+ * weights w (mask may be NULL; 1 = not used); *t0 (may be NULL) the median. */
+int mceik_l1_event(int n, const int *mask, const double *x, const double *w, double *t0, double *obj);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@
  */
 #ifndef MCEIK_EIKONAL_H_AMD
 #define MCEIK_EIKONAL_H_AMD 1
+#include <stdbool.h>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -114,6 +115,36 @@ typedef struct mceik_relocate_batch {
     int nobs;
 } mceik_relocate_batch;
 int mceik_relocate(const mceik_relocate_batch *b, void *stream);
+
+/* ---- L1 (Laplace) grid searches: the weighted-median origin time -------- */
+/* For the used observations j in order, with residual x_j and weight w_j:
+ * W = sum_j w_j, s_k = sum_j ((x_j < x_k || (x_j == x_k && j <= k)) ? w_j : 0),
+ * t0 = the smallest x_k with s_k >= 0.5 W (the lower weighted median), objfn =
+ * sum_j w_j |x_j - t0|; every sum in ascending j; no used observation: 0, 0.
+ *
+ * locate_l1_gridSearch__double64 (locate.c:1205-1335): the reference's
+ * prototype (no tcorr); host arrays, computed on the GPU.  x_j = tobs_j -
+ * test[j*ldgrd + g], w_j = 1/varobs_j; with iwantOT == 1 the weights are first
+ * multiplied by 1/W when fabs(W - 1) > 1e-14 and t0[g] is the median, otherwise
+ * t0[g] = t0use and the weights stay raw.  Deviations, where the reference is
+ * undefined or broken: masked observations are compacted away (its weight sum
+ * reads unwritten entries and its row index is wrong with a mask), its stray
+ * printf is left out, and the argument checks, messages and return codes are
+ * those of locate_l2_gridSearch__double64. */
+int locate_l1_gridSearch__double64(int ldgrd, int ngrd, int nobs, int iwantOT, double t0use,
+                                   const int *mask, const double *tobs, const double *varobs,
+                                   const double *test, double *t0, double *objfn);
+/* mceik_relocate under the L1 objective, fp32: x_j = tc_j - tables[obs_row_j][g],
+ * the raw weights wt_j (no normalisation: the sampler's convention); xnorm is
+ * ignored and may be NULL; out, t0 and log_pdf as for mceik_relocate.  With
+ * nrows > 0 an event with an obs_row outside [0, nrows) gets NaN outputs. */
+int mceik_relocate_l1(const mceik_relocate_batch *b, void *stream);
+/* The symbol the reference declares (locate.c:73) and never defines, host code:
+ * the lower weighted median of x [n] with weights w [n] as defined above.
+ * perm [n] (may be NULL) returns the indices in ascending (value, index) order;
+ * *lsort says whether that differs from perm on entry; *ierr is 1 (and 0.0 is
+ * returned) for n < 1 or a null x / w, else 0. */
+double weightedMedian__double(const int n, const double *x, const double *w, int *perm, bool *lsort, int *ierr);
 
 /* ---- batched solves on device memory ---------------------------------- */
 typedef struct mceik_fsm_batch {

@@ -210,6 +210,8 @@ EXPORTS = ("eikonal3d_serial_driver", "eikonal3d_serial_driver_sp", "eikonal3d_b
            "eikonal3d_finalize", "locate3d_gridsearch__double64", "locate3d_gridsearch__float64",
            "locate_l2_gridSearch__double64",
            "locate_l2_gridSearch__float64", "mceik_relocate",
+           "locate_l1_gridSearch__double64", "mceik_relocate_l1", "weightedMedian__double",
+           "mceik_mcmc_likelihood_set", "mceik_mcmc_likelihood_get", "mceik_l1_event",
            "locate3d_initialize", "locate3d_gridsearch", "locate3d_finalize",
            "mceik_fsm_workspace_bytes", "mceik_fsm_batch_solve", "mceik_fsm_bytes_per_node_sweep", "mceik_fsm_step_z",
            "mceik_fsm_kernel_name", "mceik_fsm_lds_bytes", "mceik_fsm_check",
@@ -308,6 +310,18 @@ def lib():
     L.locate_l2_gridSearch__float64.argtypes = [C.c_int] * 4 + [C.c_float] + [C.c_void_p] * 7
     L.mceik_relocate.restype = C.c_int
     L.mceik_relocate.argtypes = [C.POINTER(RelocateBatch), C.c_void_p]
+    L.locate_l1_gridSearch__double64.restype = C.c_int
+    L.locate_l1_gridSearch__double64.argtypes = [C.c_int] * 4 + [C.c_double] + [C.c_void_p] * 6
+    L.mceik_relocate_l1.restype = C.c_int
+    L.mceik_relocate_l1.argtypes = [C.POINTER(RelocateBatch), C.c_void_p]
+    L.weightedMedian__double.restype = C.c_double
+    L.weightedMedian__double.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_bool), pi]
+    L.mceik_l1_event.restype = C.c_int
+    L.mceik_l1_event.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, pd, pd]
+    L.mceik_mcmc_likelihood_set.restype = C.c_int
+    L.mceik_mcmc_likelihood_set.argtypes = [C.c_void_p, C.c_int]
+    L.mceik_mcmc_likelihood_get.restype = C.c_int
+    L.mceik_mcmc_likelihood_get.argtypes = [C.c_void_p]
     L.mceik_mcmc_init.restype = C.c_int
     L.mceik_mcmc_init.argtypes = [C.POINTER(MceikParms), C.POINTER(StationsStruct), C.POINTER(CatalogStruct),
                                   C.POINTER(McmcOpts), C.c_void_p, C.POINTER(C.c_void_p)]

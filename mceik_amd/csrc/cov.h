@@ -117,5 +117,6 @@ struct McmcCov;                    // a sampler's covariance state (cov.hip)
 hipError_t mcmc_cov_accumulate(McmcCov *p, const McmcDev &D, const HypoDev &H, const NuisDev &N, int chain_off, int n,
                                hipStream_t st);
 void mcmc_cov_counted(McmcCov *p);
+long long mcmc_cov_count(const McmcCov *p);   // states accumulated per chain
 bool mcmc_cov_holds_nuis(const McmcCov *p);      // a static or noise-index probe is registered
 void mcmc_cov_free(McmcCov *p);

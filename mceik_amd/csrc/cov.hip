@@ -203,6 +203,8 @@ struct McmcCov {
 
 void mcmc_cov_counted(McmcCov *p) { p->n++; }
 
+long long mcmc_cov_count(const McmcCov *p) { return p->n; }
+
 bool mcmc_cov_holds_nuis(const McmcCov *p) { return probes_hold_nuis(p->probes); }
 
 void mcmc_cov_free(McmcCov *p)

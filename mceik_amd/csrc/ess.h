@@ -48,5 +48,6 @@ int mcmc_ess_k(const McmcEss *p);
 hipError_t mcmc_ess_accumulate(McmcEss *p, const McmcDev &D, const HypoDev &H, const NuisDev &N, int chain_off, int n,
                                int k, hipStream_t st);
 void mcmc_ess_counted(McmcEss *p);
+long long mcmc_ess_count(const McmcEss *p);   // states accumulated per chain
 bool mcmc_ess_holds_nuis(const McmcEss *p);      // a static or noise-index probe is registered
 void mcmc_ess_free(McmcEss *p);

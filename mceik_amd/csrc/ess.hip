@@ -158,6 +158,8 @@ struct McmcEss {
 
 void mcmc_ess_counted(McmcEss *p) { p->n++; }
 
+long long mcmc_ess_count(const McmcEss *p) { return p->n; }
+
 int mcmc_ess_k(const McmcEss *p) { return __builtin_ctzll((unsigned long long)(p->n + 1)); }
 
 bool mcmc_ess_holds_nuis(const McmcEss *p) { return probes_hold_nuis(p->probes); }

@@ -45,4 +45,5 @@ struct McmcFit;                    // a sampler's data-fit state (fit.hip)
 hipError_t mcmc_fit_accumulate(McmcFit *p, const McmcDev &D, const HypoDev &H, const NuisDev &N, int chain_off, int n,
                                hipStream_t st);
 void mcmc_fit_counted(McmcFit *p);
+long long mcmc_fit_count(const McmcFit *p);   // states accumulated per chain
 void mcmc_fit_free(McmcFit *p);

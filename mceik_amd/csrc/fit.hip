@@ -72,17 +72,24 @@ __global__ __launch_bounds__(256) void fit_residual_kernel(McmcDev D, NuisDev N,
     int nused = 0;
     for (int j = j0; j < j1; j++)
         if (!E.obs_mask[j]) { xnorm = xnorm + 1.0 / mcmcd::ldv(&E.var[j]); nused++; }
-    for (int j = j0; j < j1; j++) {
-        if (E.obs_mask[j]) continue;
-        const double te = te_of(j);
-        const double tc = E.tobs[j] - mcmcd::ldv(&E.tcorr[j]);
-        t0 = t0 + ((1.0 / mcmcd::ldv(&E.var[j])) / xnorm) * (tc - te);
+    if (E.l1) {
+        // the L1 likelihood: the origin time is the weighted median of the logL (event_obj_l1's arithmetic)
+        t0 = l1::median<double>(j0, j1, [&](int j) -> bool { return !E.obs_mask[j]; },
+                                [&](int j) -> double { return (E.tobs[j] - mcmcd::ldv(&E.tcorr[j])) - te_of(j); },
+                                [&](int j) -> double { return 1.0 / mcmcd::ldv(&E.var[j]); }, nullptr);
+    } else {
+        for (int j = j0; j < j1; j++) {
+            if (E.obs_mask[j]) continue;
+            const double te = te_of(j);
+            const double tc = E.tobs[j] - mcmcd::ldv(&E.tcorr[j]);
+            t0 = t0 + ((1.0 / mcmcd::ldv(&E.var[j])) / xnorm) * (tc - te);
+        }
     }
     for (int j = j0; j < j1; j++) {
         if (E.obs_mask[j]) { q[j] = 0; zq[j] = 0; bin[j] = -1; continue; }
         const double te = te_of(j);
         const double tc = E.tobs[j] - mcmcd::ldv(&E.tcorr[j]);
-        const double r = tc - (te + t0);
+        const double r = E.l1 ? (tc - te) - t0 : tc - (te + t0);
         const double z = (1.0 / mcmcd::ldv(&E.var[j])) * r;
         q[j] = fit_sat32(r * F.inv_tick, nsq);
         zq[j] = fit_sat32(z * FIT_ZSCALE, nsz);
@@ -165,6 +172,8 @@ struct McmcFit {
 };
 
 void mcmc_fit_counted(McmcFit *p) { p->n++; }
+
+long long mcmc_fit_count(const McmcFit *p) { return p->n; }
 
 static void **fit_array(McmcFit *p, int which)
 {

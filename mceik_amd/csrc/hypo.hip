@@ -62,6 +62,10 @@ __device__ __forceinline__ double hypo_event_obj(const McmcDev &D, const HypoDev
         return (double)tt[((size_t)ph * D.nstat + D.obs_stat[j]) * nev2 + col];
     };
     const int j0 = D.obs_ptr[e], j1 = D.obs_ptr[e + 1];
+    if (D.l1)                       // the L1 likelihood: mcmc_device.h event_obj_l1's arithmetic
+        return l1::event<double>(j0, j1, [&](int j) -> bool { return !D.obs_mask[j]; },
+                                 [&](int j) -> double { return (D.tobs[j] - D.tcorr[j]) - te_of(j); },
+                                 [&](int j) -> double { return 1.0 / D.var[j]; }, nullptr);
     double xnorm = 0.0, t0 = 0.0, obj = 0.0;
     for (int j = j0; j < j1; j++) if (!D.obs_mask[j]) xnorm = xnorm + 1.0 / D.var[j];
     for (int j = j0; j < j1; j++) {

@@ -27,6 +27,7 @@ struct McmcDev {
     double *keep_logl;             // [max_samples][keep_stride]
     int keep_stride;               // chains per kept slot: the sampler's nchains (a pipe's view covers a part)
     const double *beta;            // [nchains] inverse temperature per chain (parallel tempering), null: off
+    int l1;                        // the likelihood's norm is 1 (Laplace, l1.h); 0: the L2 misfit
 };
 
 // One rank's chain shard as the checkpoint gather sees it (sampler_api.hip

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "l1.h"
 #include "mcmc_common.h"
 
 namespace mcmcd {
@@ -138,10 +139,32 @@ __device__ __forceinline__ double event_obj(const McmcDev &D, int c, int pph, in
     return obj;
 }
 
+// objfn of event e for chain c under the L1 (Laplace) likelihood (D.l1;
+// DESIGN.md s.23): l1.h's event objective of the residuals x_j = (tobs_j -
+// tcorr_j) - te_j with the raw weights 1 / var_j, at their weighted median.
+// Tables as in event_obj.  The multi-step kernel's epilogue does not call it.
+__device__ __forceinline__ double event_obj_l1(const McmcDev &D, int c, int pph, int e)
+{
+    const float *tp = D.ttab + (size_t)c * D.nstat * D.nev;
+    const float *tcur = D.ttab_cur ? D.ttab_cur + (size_t)c * D.nphase * D.nstat * D.nev : nullptr;
+    auto x_of = [&](int j) -> double {
+        const int ph = D.obs_phase ? D.obs_phase[j] : 0;
+        const size_t k = (size_t)D.obs_stat[j] * D.nev + e;
+        const double te = (double)(ph == pph ? ldv(tp + k) : ldv(tcur + (size_t)ph * D.nstat * D.nev + k));
+        return (D.tobs[j] - D.tcorr[j]) - te;
+    };
+    return l1::event<double>(D.obs_ptr[e], D.obs_ptr[e + 1], [&](int j) -> bool { return !D.obs_mask[j]; }, x_of,
+                             [&](int j) -> double { return 1.0 / D.var[j]; }, nullptr);
+}
+
 // logL = -sum_e objfn_e, events in order.
 __device__ __forceinline__ double chain_loglik(const McmcDev &D, int c, int pph)
 {
     double logl = 0.0;
+    if (D.l1) {
+        for (int e = 0; e < D.nev; e++) logl = logl - event_obj_l1(D, c, pph, e);
+        return logl;
+    }
     for (int e = 0; e < D.nev; e++) logl = logl - event_obj(D, c, pph, e);
     return logl;
 }

@@ -46,6 +46,10 @@ __device__ __forceinline__ double nuis_event_obj(const McmcDev &D, const NuisDev
         return N.tcorr0[j] + (double)kc * N.dt;
     };
     const int j0 = D.obs_ptr[e], j1 = D.obs_ptr[e + 1];
+    if (D.l1)                       // the L1 likelihood: mcmc_device.h event_obj_l1's arithmetic on the candidate
+        return l1::event<double>(j0, j1, [&](int j) -> bool { return !D.obs_mask[j]; },
+                                 [&](int j) -> double { return (D.tobs[j] - tcorr_of(j)) - te_of(j); },
+                                 [&](int j) -> double { return 1.0 / var_of(j); }, nullptr);
     double xnorm = 0.0, t0 = 0.0, obj = 0.0;
     for (int j = j0; j < j1; j++) if (!D.obs_mask[j]) xnorm = xnorm + 1.0 / var_of(j);
     for (int j = j0; j < j1; j++) {

@@ -233,11 +233,12 @@ int temper_round(mceik_mcmc *s, int parity);
 // Voronoi-cell models (a velocity step rasters the proposed nuclei before its
 // forward, and the multi-step kernel's epilogue knows no nuclei); the
 // data-fit sums of a one-model sampler (they read the chains' current tables,
-// which the multi-step kernel's epilogue keeps for two models only).
+// which the multi-step kernel's epilogue keeps for two models only); the L1
+// likelihood (the multi-step kernel's epilogue evaluates the L2 misfit only).
 static inline bool mcmc_multi_step(const mceik_mcmc *s)
 {
     return s->persist && !s->block_on && !s->prior_on && !s->hypo_on && !s->N.kn && !s->lang_on && !s->de_on && !s->vor_on &&
-           !(s->fit_on && s->D.nphase == 1);
+           !(s->fit_on && s->D.nphase == 1) && !s->D.l1;
 }
 // A one-model sampler's current tables (sampler_api.hip).  hold: while nuisance
 // state is held or the data-fit sums are on, D.ttab_cur = ttab_cur1 (allocated

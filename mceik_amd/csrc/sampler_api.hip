@@ -83,6 +83,45 @@ int mcmc_tables1_drop(mceik_mcmc *s)
 }
 
 // ---------------------------------------------------------------------------
+// the likelihood's norm (include/mceik.h mceik_mcmc_likelihood_*)
+
+// An enabled accumulator of kept states holds some: a change of what the
+// chains sample would mix two posteriors in its sums.
+static const char *kept_stream_holding(const mceik_mcmc *s)
+{
+    if (post_holds_states(s)) return "the streaming posterior";
+    if (s->cov && s->cov_on && mcmc_cov_count(s->cov) > 0) return "the covariance sums";
+    if (s->ess && s->ess_on && mcmc_ess_count(s->ess) > 0) return "the batch-means sums";
+    if (s->fit && s->fit_on && mcmc_fit_count(s->fit) > 0) return "the data-fit sums";
+    if (s->hypo_on && s->hyp_n > 0) return "the hypocentre moments";
+    if (s->nuis_on && s->nuis_n > 0) return "the noise / statics moments";
+    if (s->vor_on && s->vor_n > 0) return "the Voronoi-cell moments";
+    return nullptr;
+}
+
+extern "C" int mceik_mcmc_likelihood_set(mceik_mcmc *s, int norm)
+{
+    if (!s || (norm != 1 && norm != 2)) return 1;
+    const char *who = "mceik_mcmc_likelihood_set";
+    if (s->lang_on) {
+        fprintf(stderr, "%s: Langevin moves are on: their gradient is the L2 misfit's\n", who);
+        return 1;
+    }
+    if (const char *what = kept_stream_holding(s)) {
+        fprintf(stderr, "%s: %s already hold states of the other likelihood\n", who, what);
+        return 1;
+    }
+    if ((s->D.l1 != 0) == (norm == 1)) return 0;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    s->D.l1 = norm == 1 ? 1 : 0;
+    if (pipes_refresh(s)) return -1;
+    return forward_logl(s, who);       // every chain's logL under the new norm; step counter and models untouched
+}
+
+extern "C" int mceik_mcmc_likelihood_get(const mceik_mcmc *s) { return s ? (s->D.l1 ? 1 : 2) : 0; }
+
+// ---------------------------------------------------------------------------
 // parallel tempering (include/mceik.h mceik_mcmc_temper_*)
 
 extern "C" int mceik_temper_ladder(int ntemps, double tmax, double *beta)
@@ -860,6 +899,11 @@ extern "C" int mceik_mcmc_lang_enable(mceik_mcmc *s, const mceik_lang_opts *o)
 {
     if (!s || !o) return 1;
     if (vor_refuses(s, "mceik_mcmc_lang_enable")) return 1;
+    if (s->D.l1) {
+        fprintf(stderr, "mceik_mcmc_lang_enable: the L1 likelihood is on (mceik_mcmc_likelihood_set): the gradient of "
+                        "its piecewise-linear objective is not provided\n");
+        return 1;
+    }
     if (o->every <= 0 || o->offset < 0 || o->offset >= o->every || !(o->sigma > 0.0 && o->sigma <= DBL_MAX) ||
         o->dmax < 1 || o->dmax > MCEIK_LANG_DMAX)
         return 1;

@@ -109,6 +109,19 @@ def locate_l2_gridsearch(ldgrd, ngrd, nobs, iwantOT, t0use, mask, tobs, tcorr, v
                                             objfn.ctypes.data_as(C.c_void_p))
 
 
+def locate_l1_gridsearch(ldgrd, ngrd, nobs, iwantOT, t0use, mask, tobs, varobs, test, t0, objfn):
+    """locate_l1_gridSearch__double64 (locate.c:1205-1335: the L1 misfit with the
+    weighted-median origin time) on the GPU; returns ierr.  t0/objfn/test must be
+    64-byte aligned float64 arrays, as for `locate_l2_gridsearch`."""
+    L = _lib.lib()
+    m = None if mask is None else np.ascontiguousarray(mask, dtype=np.int32)
+    f = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+    to, va = f(tobs), f(varobs)
+    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    return L.locate_l1_gridSearch__double64(int(ldgrd), int(ngrd), int(nobs), int(iwantOT), float(t0use),
+                                            p(m), p(to), p(va), p(test), p(t0), p(objfn))
+
+
 def locate_l2_gridsearch_f32(ldgrd, ngrd, nobs, iwantOT, t0use, mask, tobs, tcorr, varobs, test, t0, objfn):
     """locate_l2_gridSearch__float64 (locate.c:1079-1203, the fp32 variant) on the
     GPU; returns ierr.  test/t0/objfn: 64-byte aligned float32 arrays."""
@@ -122,7 +135,7 @@ def locate_l2_gridsearch_f32(ldgrd, ngrd, nobs, iwantOT, t0use, mask, tobs, tcor
 
 
 def relocate(tables, events, ldgrd=None, iwantOT=1, t0use=0.0, log_pdf=True, stream=0, single_pass=True,
-             want_t0=True):
+             want_t0=True, norm=2):
     """Relocation grid search (SURVEY s.8f row 2) of many events against one
     model's travel-time tables, one GPU launch (mceik_relocate).
 
@@ -133,7 +146,11 @@ def relocate(tables, events, ldgrd=None, iwantOT=1, t0use=0.0, log_pdf=True, str
              in the reference's observation order
     returns (out, t0): torch float32 [nev, ldgrd]; out = -objfn if log_pdf
     else objfn (locate.c L2 with the analytic origin time, fp32).
+    norm=1: the L1 objective with the weighted-median origin time and the raw
+    weights 1 / var instead (mceik_relocate_l1; fp32).
     """
+    if norm not in (1, 2):
+        raise ValueError("norm: 1 or 2")
     import torch
     L = _lib.lib()
     dev = tables.device
@@ -170,7 +187,11 @@ def relocate(tables, events, ldgrd=None, iwantOT=1, t0use=0.0, log_pdf=True, str
     b.t0, b.out, b.log_pdf = (t0.data_ptr() if want_t0 else None), out.data_ptr(), 1 if log_pdf else 0
     if single_pass:
         b.nrows, b.nobs = int(nrows), len(rows)
-    if L.mceik_relocate(C.byref(b), C.c_void_p(stream)) != 0:
+    if norm == 1:
+        b.xnorm = None
+        if L.mceik_relocate_l1(C.byref(b), C.c_void_p(stream)) != 0:
+            raise RuntimeError("mceik_relocate_l1 failed")
+    elif L.mceik_relocate(C.byref(b), C.c_void_p(stream)) != 0:
         raise RuntimeError("mceik_relocate failed")
     return out, (t0 if want_t0 else None)
 

@@ -682,6 +682,28 @@ class Sampler:
                 "workspace_bytes": list(i.workspace_bytes[:n]), "lds_bytes": int(i.lds_bytes),
                 "masked_s": i.masked_s, "kernel": i.kernel.decode(), "multi_step": bool(i.multi_step)}
 
+    def likelihood_set(self, norm):
+        """The likelihood's norm (mceik_mcmc_likelihood_set): 2 the
+        weighted L2 misfit with the analytic origin time (default), 1 a Laplace
+        density of scale var per pick with the weighted-median origin time.  Every
+        chain's logL is recomputed with one full forward; models and step counter
+        stay.  Refused (ValueError, nothing changed) for another norm, while
+        Langevin moves are on, or while an enabled accumulator of kept states
+        already holds states.  While norm = 1, `lang_enable` and `logl_grad` are
+        refused and every step is a launch of its own."""
+        rc = self._L.mceik_mcmc_likelihood_set(self._h, int(norm))
+        if rc == 1:
+            raise ValueError(f"likelihood_set({norm!r}) refused: norm is 1 or 2; Langevin moves must be off and no "
+                             "enabled accumulator of kept states may hold states")
+        if rc != 0:
+            raise RuntimeError(f"mceik_mcmc_likelihood_set failed ({rc})")
+        self._last_full = True
+
+    @property
+    def likelihood(self):
+        """The likelihood's norm: 1 (Laplace) or 2 (Gaussian)."""
+        return int(self._L.mceik_mcmc_likelihood_get(self._h))
+
     def state(self):
         v = np.empty(self.model_shape, np.int32)
         logl = np.empty(self.nchains, np.float64)
@@ -737,7 +759,8 @@ class Sampler:
                                          nacc.ctypes.data_as(C.c_void_p), C.byref(step), C.byref(nkept)) != 0:
             raise RuntimeError("mceik_mcmc_checkpoint failed")
         ck = {"v": v, "logl": logl, "naccept": nacc, "step": step.value, "nkept": nkept.value,
-              "chain_offset": self.chain_offset, "seed": self.p.seed}
+              "chain_offset": self.chain_offset, "seed": self.p.seed,
+              "likelihood": self.likelihood}      # the norm decides what logl means
         if self._post is not None:       # the accumulators belong to the state of a run that summarises itself
             ck["posterior"] = self.posterior_raw()
         if self._temper is not None:     # the ladder decides what the chains sample; the counters ride along
@@ -777,6 +800,8 @@ class Sampler:
         """Load a checkpoint() dict (mceik_mcmc_restore)."""
         if ck.get("chain_offset", self.chain_offset) != self.chain_offset or ck.get("seed", self.p.seed) != self.p.seed:
             raise ValueError("checkpoint belongs to another chain shard or seed")
+        if int(ck.get("likelihood", 2)) != self.likelihood:      # a checkpoint without the entry is L2
+            raise ValueError("the checkpoint was taken under the other likelihood norm (likelihood_set)")
         tk = ck.get("temper")            # a checkpoint without the entry carries no ladder and restores anywhere
         if tk is not None:
             mine = self._temper
@@ -2416,7 +2441,9 @@ class FitSummary:
     """The data side of a run from merged `FitPartials`.  Per pick [nobs]:
     `pick_mean`, `pick_sd` (seconds) of the residual tobs - tcorr - (te + t0)
     and `pick_zmean`, `pick_zrms` of the standardised residual z (rms about 1
-    where the noise level is right).  Per event [nev]: `t0_mean`, `t0_sd` (the
+    where the noise level is right; under the L1 likelihood, `likelihood_set(1)`,
+    var is a Laplace scale, the expected z^2 is 2, and t0 is the weighted median).
+    Per event [nev]: `t0_mean`, `t0_sd` (the
     origin time, t0_ref added back) and `ev_misfit`, the mean over states of
     sum z^2 / (used picks - 1).  Per (phase, station) [nphase, nstat]:
     `sta_mean` (the mean residual: the data's estimate of a station static),
@@ -2463,10 +2490,50 @@ def picks_from_forward(device=0, precision=64):
     return f
 
 
-def _pick_terms(p: Problem, ttab, var, tcorr, with_t0=False):
+def weighted_median(x, w):
+    """The lower weighted median of x with weights w (weightedMedian__double, the
+    library's host code; csrc/l1.h): the smallest x_k whose weights at or below
+    it, in (value, index) order, reach half the total."""
+    x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+    w = np.ascontiguousarray(w, dtype=np.float64).ravel()
+    if x.size < 1 or x.size != w.size:
+        raise ValueError("weighted_median: x and w of one length >= 1")
+    ierr = C.c_int(0)
+    t = _lib.lib().weightedMedian__double(int(x.size), x.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p),
+                                          None, None, C.byref(ierr))
+    if ierr.value != 0:
+        raise RuntimeError("weightedMedian__double failed")
+    return float(t)
+
+
+def l1_event(x, w, mask=None):
+    """(t0, objfn) of one event under the L1 likelihood (mceik_l1_event, the
+    library's host code; csrc/l1.h): t0 the lower weighted median of the used
+    residuals x with weights w, objfn = sum w |x - t0| in order; (0, 0) when no
+    entry is used.  mask: 1 = not used."""
+    x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+    w = np.ascontiguousarray(w, dtype=np.float64).ravel()
+    if x.size != w.size:
+        raise ValueError("l1_event: x and w of one length")
+    m = None if mask is None else np.ascontiguousarray(mask, dtype=np.int32).ravel()
+    if m is not None and m.size != x.size:
+        raise ValueError("l1_event: mask of the length of x")
+    t0, obj = C.c_double(0.0), C.c_double(0.0)
+    if _lib.lib().mceik_l1_event(int(x.size), None if m is None else m.ctypes.data_as(C.c_void_p),
+                                 x.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p), C.byref(t0),
+                                 C.byref(obj)) != 0:
+        raise RuntimeError("mceik_l1_event failed")
+    return t0.value, obj.value
+
+
+def _pick_terms(p: Problem, ttab, var, tcorr, with_t0=False, norm=2):
     """event_obj's arithmetic (csrc/mcmc_device.h) on the host, operation for
     operation in fp64: per event the used picks, their weights 1 / var, xnorm,
-    the residuals tc - (te + t0) and objfn (with_t0: and, sixth, t0)."""
+    the residuals tc - (te + t0) and objfn (with_t0: and, sixth, t0).  norm=1:
+    event_obj_l1's (csrc/l1.h through `l1_event`): the third entry is the sum
+    of the weights, t0 the weighted median, the residuals (tc - te) - t0."""
+    if norm not in (1, 2):
+        raise ValueError("norm: 1 or 2")
     tt = np.asarray(ttab, dtype=np.float32).astype(np.float64).reshape(max(1, p.nphase), p.nstat, p.nevents)
     var = np.asarray(p.var if var is None else var, dtype=np.float64)
     tcorr = np.asarray(p.tcorr if tcorr is None else tcorr, dtype=np.float64)
@@ -2475,6 +2542,15 @@ def _pick_terms(p: Problem, ttab, var, tcorr, with_t0=False):
     out = []
     for e in range(p.nevents):
         js = [j for j in range(int(ptr[e]), int(ptr[e + 1])) if not mask[j]]
+        if norm == 1:
+            w = [1.0 / float(var[j]) for j in js]
+            x = [(float(tobs[j]) - float(tcorr[j])) - float(tt[phase[j], stat[j], e]) for j in js]
+            wsum = 0.0
+            for wj in w:
+                wsum = wsum + wj
+            t0, obj = l1_event(x, w)
+            out.append((js, w, wsum, [xj - t0 for xj in x], obj) + ((t0,) if with_t0 else ()))
+            continue
         xnorm = 0.0
         for j in js:
             xnorm = xnorm + 1.0 / float(var[j])
@@ -2493,13 +2569,14 @@ def _pick_terms(p: Problem, ttab, var, tcorr, with_t0=False):
     return out
 
 
-def logl_picks(p: Problem, ttab, var=None, tcorr=None):
+def logl_picks(p: Problem, ttab, var=None, tcorr=None, norm=2):
     """logL = ((0 - objfn_0) - objfn_1) - ... of the tables ttab [nphase, nstat,
     nev] ([nstat, nev] with one model): the sampler's value bit for bit (the
     noise normalisation of DESIGN.md s.15 is the caller's).  var, tcorr [nobs]:
-    effective values (None: the catalogue's)."""
+    effective values (None: the catalogue's).  norm: the likelihood's
+    (`Sampler.likelihood_set`)."""
     logl = 0.0
-    for _, _, _, _, obj in _pick_terms(p, ttab, var, tcorr):
+    for _, _, _, _, obj in _pick_terms(p, ttab, var, tcorr, norm=norm):
         logl = logl - obj
     return logl
 
@@ -2567,6 +2644,9 @@ def logl_grad(smp: "Sampler", chains=None, wrt="slowness", chunk=None):
     from .eikonal import BatchSolver
     if wrt not in ("slowness", "velocity"):
         raise ValueError(f"wrt: 'slowness' or 'velocity', not {wrt!r}")
+    if smp.likelihood != 2:
+        raise ValueError("logl_grad: the sampler's likelihood is L1 (likelihood_set): the gradient of its "
+                         "piecewise-linear objective is not provided")
     p = smp.p
     chains = list(range(smp.nchains)) if chains is None else [int(c) for c in chains]
     nph, nstat, nev, ncell = max(1, p.nphase), p.nstat, p.nevents, p.ncell
