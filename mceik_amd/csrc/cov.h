@@ -7,6 +7,7 @@
 
 #include "../../include/mceik.h"
 #include "hypo.h"
+#include "kept.h"
 #include "mcmc_common.h"
 #include "nuis.h"
 
@@ -17,7 +18,7 @@
 // Wrap bound: a word wraps after 2^63 / (max |x| * vmax) accumulated states
 // (chains x kept steps), more than 1e11 at the default prior (|x|, v <= 9000).
 // Per-chain arrays are indexed by the sampler's chain; a pipe's launch offsets
-// them (mcmc_cov_accumulate's chain_off).  The pooled sums are shared: pipes
+// them (cov.hip cov_accumulate's chain_off).  The pooled sums are shared: pipes
 // add atomically.
 struct CovDev {
     int np, within, ncm;
@@ -107,16 +108,5 @@ static inline bool probes_upload(ProbeList &L, int n, const int *kind, const int
                    hipMemcpy(L.d + n, index, n * sizeof(int), hipMemcpyHostToDevice) == hipSuccess));
 }
 
-struct McmcCov;                    // a sampler's covariance state (cov.hip)
-
-// The kept-state hook's side (sampler.hip kept_queue), in posterior.h's
-// convention: the first n chains of view D / H / N, which are chains
-// [chain_off, chain_off + n) of the sampler, added on stream st (two launches:
-// the probe gather, then the rank-n update); once every chain of a kept step
-// is queued, count the state.
-hipError_t mcmc_cov_accumulate(McmcCov *p, const McmcDev &D, const HypoDev &H, const NuisDev &N, int chain_off, int n,
-                               hipStream_t st);
-void mcmc_cov_counted(McmcCov *p);
-long long mcmc_cov_count(const McmcCov *p);   // states accumulated per chain
-bool mcmc_cov_holds_nuis(const McmcCov *p);      // a static or noise-index probe is registered
-void mcmc_cov_free(McmcCov *p);
+// The covariances' row of mceik_mcmc::kept (kept.h), off.
+KeptStream mcmc_cov_stream();

@@ -196,29 +196,38 @@ __global__ __launch_bounds__(64) void cov_reduce_kernel(CovDev V, const long lon
 struct McmcCov {
     CovDev V;                      // every chain of the sampler
     int nchains;
-    long long n;                   // states accumulated per chain
     ProbeList probes;
     unsigned long long *d_T, *d_P, *d_PA;   // within: partials scratch [np][ncm][2], [ncm][2], [np][np][2]
 };
 
-void mcmc_cov_counted(McmcCov *p) { p->n++; }
-
-long long mcmc_cov_count(const McmcCov *p) { return p->n; }
-
-bool mcmc_cov_holds_nuis(const McmcCov *p) { return probes_hold_nuis(p->probes); }
-
-void mcmc_cov_free(McmcCov *p)
+static int cov_arrays(void *state, KeptArray out[KEPT_MAX_ARRAYS])     // A, G, S, Q, C and, within, Ac, Sc
 {
-    if (!p) return;
-    void *all[] = {p->probes.d, p->V.X, p->V.A, p->V.G, p->V.S, p->V.Q, p->V.C, p->V.Ac, p->V.Sc, p->d_T, p->d_P, p->d_PA};
+    McmcCov *p = (McmcCov *)state;
+    const size_t np = p->V.np, ncm = p->V.ncm, nch = p->nchains;
+    long long **a[7] = {&p->V.A, &p->V.G, &p->V.S, &p->V.Q, &p->V.C, &p->V.Ac, &p->V.Sc};
+    const size_t w[7] = {np, np * np, ncm, ncm, np * ncm, nch * np, nch * ncm};
+    const int na = p->V.within ? 7 : 5;
+    for (int k = 0; k < na; k++) out[k] = {(void **)a[k], w[k] * 8, 0};
+    return na;
+}
+
+static bool cov_holds_nuis(const void *state) { return probes_hold_nuis(((const McmcCov *)state)->probes); }
+
+static void cov_free_extra(void *state)
+{
+    McmcCov *p = (McmcCov *)state;
+    void *all[] = {p->probes.d, p->V.X, p->d_T, p->d_P, p->d_PA};
     for (void *q : all)
         if (q) hipFree(q);
     delete p;
 }
 
-hipError_t mcmc_cov_accumulate(McmcCov *p, const McmcDev &D, const HypoDev &H, const NuisDev &N, int chain_off, int n,
-                               hipStream_t st)
+// The kept-state hook's side (kept.h KeptStream::accumulate): two launches,
+// the probe gather, then the rank-n update.
+static hipError_t cov_accumulate(void *state, const McmcDev &D, const HypoDev &H, const NuisDev &N, int chain_off, int n,
+                                 long long, hipStream_t st)
 {
+    const McmcCov *p = (const McmcCov *)state;
     if (n <= 0) return hipSuccess;
     CovDev V = p->V;                   // the chains' rows of the per-chain arrays
     V.X += (size_t)chain_off * V.np;
@@ -233,17 +242,15 @@ hipError_t mcmc_cov_accumulate(McmcCov *p, const McmcDev &D, const HypoDev &H, c
     return hipGetLastError();
 }
 
-static size_t cov_words(const McmcCov *p, int which)    // words of A, G, S, Q, C, Ac, Sc
+KeptStream mcmc_cov_stream()
 {
-    const size_t np = p->V.np, ncm = p->V.ncm, nch = p->nchains;
-    const size_t w[7] = {np, np * np, ncm, ncm, np * ncm, nch * np, nch * ncm};
-    return w[which];
-}
-
-static long long **cov_array(McmcCov *p, int which)
-{
-    long long **a[7] = {&p->V.A, &p->V.G, &p->V.S, &p->V.Q, &p->V.C, &p->V.Ac, &p->V.Sc};
-    return a[which];
+    KeptStream k = {};
+    k.name = "the covariance sums";
+    k.arrays = cov_arrays;
+    k.accumulate = cov_accumulate;
+    k.free_extra = cov_free_extra;
+    k.holds_nuis = cov_holds_nuis;
+    return k;
 }
 
 static bool cov_same(const McmcCov *p, const mceik_cov_opts *o)
@@ -271,104 +278,53 @@ extern "C" int mceik_mcmc_cov_enable(mceik_mcmc *s, const mceik_cov_opts *o)
         const long long hi = mcmc_probe_limit(s, o->kind[k]);
         if (hi < 0 || o->index[k] < 0 || o->index[k] >= hi) return 1;   // (a probe whose state is not held has no valid index)
     }
-    McmcCov *p = s->cov;
-    if (p && !cov_same(p, o) && p->n > 0) return 1;
+    KeptStream &k = s->kept[KEPT_COV];
+    const int rc = kept_enable_held(s, k, k.state && cov_same((const McmcCov *)k.state, o), "mceik_mcmc_cov_enable");
+    if (rc != KEPT_REPLACE) return rc;
     DeviceScope dg(s->device);
-    if (p && cov_same(p, o)) {                      // the held sums go on
-        s->cov_on = true;
-        return 0;
-    }
-    HIPCHK(hipStreamSynchronize(s->stream));
-    s->cov = nullptr;
-    s->cov_on = false;
-    mcmc_cov_free(p);
-    p = new McmcCov();
+    McmcCov *p = new McmcCov();
     memset(p, 0, sizeof(*p));
     p->V.np = o->np;
     p->V.within = o->within ? 1 : 0;
     p->V.ncm = D.ncm;
     p->nchains = D.nchains;
-    const size_t np = o->np, ncm = D.ncm;
-    bool ok = probes_upload(p->probes, o->np, o->kind, o->index) &&
-              hipMalloc((void **)&p->V.X, (size_t)D.nchains * np * sizeof(int)) == hipSuccess;
-    for (int a = 0; a < (p->V.within ? 7 : 5) && ok; a++) {
-        ok = hipMalloc((void **)cov_array(p, a), cov_words(p, a) * 8) == hipSuccess &&
-             hipMemset(*cov_array(p, a), 0, cov_words(p, a) * 8) == hipSuccess;
-    }
+    const size_t np = o->np, ncm = D.ncm, xbytes = (size_t)D.nchains * np * sizeof(int);
+    KeptArray a[KEPT_MAX_ARRAYS];
+    bool ok = probes_upload(p->probes, o->np, o->kind, o->index) && hipMalloc((void **)&p->V.X, xbytes) == hipSuccess &&
+              hipMemset(p->V.X, 0, xbytes) == hipSuccess && kept_arrays_alloc(a, cov_arrays(p, a));
     if (ok && p->V.within)
         ok = hipMalloc((void **)&p->d_T, np * ncm * 16) == hipSuccess && hipMalloc((void **)&p->d_P, ncm * 16) == hipSuccess &&
              hipMalloc((void **)&p->d_PA, np * np * 16) == hipSuccess;
-    if (ok) ok = hipMemset(p->V.X, 0, (size_t)D.nchains * np * sizeof(int)) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
         fprintf(stderr, "mceik_mcmc_cov_enable: out of device memory (%zu B of accumulators)\n",
                 8 * ((np + 2) * ncm + (p->V.within ? (size_t)D.nchains * (ncm + np) : 0)));
-        mcmc_cov_free(p);
+        kept_state_free(k, p);
         return -1;
     }
     p->V.kind = p->probes.d;
     p->V.index = p->probes.d + np;
-    s->cov = p;
-    s->cov_on = true;
-    return 0;
+    return kept_publish(s, k, p, "mceik_mcmc_cov_enable");
 }
 
-extern "C" int mceik_mcmc_cov_disable(mceik_mcmc *s)
-{
-    if (!s) return 1;
-    s->cov_on = false;                 // host state only: queued steps keep the kernels they were queued with
-    return 0;
-}
+extern "C" int mceik_mcmc_cov_disable(mceik_mcmc *s) { return s ? kept_disable(s, s->kept[KEPT_COV]) : 1; }
 
-extern "C" int mceik_mcmc_cov_clear(mceik_mcmc *s)
-{
-    if (!s) return 1;
-    if (!s->cov) return 0;
-    DeviceScope dg(s->device);
-    const hipError_t e = hipStreamSynchronize(s->stream);
-    mcmc_cov_free(s->cov);
-    s->cov = nullptr;
-    s->cov_on = false;
-    return e == hipSuccess ? 0 : -1;
-}
+extern "C" int mceik_mcmc_cov_clear(mceik_mcmc *s) { return s ? kept_clear(s, s->kept[KEPT_COV]) : 1; }
 
-extern "C" int mceik_mcmc_cov_accumulate(mceik_mcmc *s)
-{
-    if (!s || !s->cov || !s->cov_on) return 1;
-    DeviceScope dg(s->device);
-    HIPCHK(mcmc_cov_accumulate(s->cov, s->D, s->H, s->N, 0, temper_cold(s), s->stream));   // tempering: the cold chains
-    mcmc_cov_counted(s->cov);
-    return 0;
-}
+extern "C" int mceik_mcmc_cov_accumulate(mceik_mcmc *s) { return s ? kept_accumulate(s, s->kept[KEPT_COV]) : 1; }
 
 extern "C" int mceik_mcmc_cov_get(mceik_mcmc *s, long long *n, long long *A, long long *G, long long *S, long long *Q,
                                   long long *C, long long *Ac, long long *Sc)
 {
-    if (!s || !s->cov) return 1;
-    McmcCov *p = s->cov;
-    if (mceik_mcmc_sync(s)) return -1;
-    DeviceScope dg(s->device);
-    if (n) *n = p->n;
-    long long *dst[7] = {A, G, S, Q, C, Ac, Sc};
-    for (int a = 0; a < (p->V.within ? 7 : 5); a++)
-        if (dst[a]) HIPCHK(hipMemcpy(dst[a], *cov_array(p, a), cov_words(p, a) * 8, hipMemcpyDeviceToHost));
-    return 0;
+    void *const host[] = {A, G, S, Q, C, Ac, Sc};
+    return s ? kept_get(s, s->kept[KEPT_COV], n, host) : 1;
 }
 
 extern "C" int mceik_mcmc_cov_set(mceik_mcmc *s, long long n, const long long *A, const long long *G, const long long *S,
                                   const long long *Q, const long long *C, const long long *Ac, const long long *Sc)
 {
-    if (!s || !s->cov || n < 0) return 1;
-    McmcCov *p = s->cov;
-    const long long *src[7] = {A, G, S, Q, C, Ac, Sc};
-    const int na = p->V.within ? 7 : 5;
-    for (int a = 0; a < na; a++)
-        if (!src[a]) return 1;
-    DeviceScope dg(s->device);
-    HIPCHK(hipStreamSynchronize(s->stream));
-    for (int a = 0; a < na; a++) HIPCHK(hipMemcpy(*cov_array(p, a), src[a], cov_words(p, a) * 8, hipMemcpyHostToDevice));
-    p->n = n;
-    return 0;
+    const void *const host[] = {A, G, S, Q, C, Ac, Sc};
+    return s ? kept_set(s, s->kept[KEPT_COV], n, host) : 1;
 }
 
 // int64 words widened to 128-bit two's complement (lo, hi).
@@ -382,8 +338,8 @@ static void cov_widen(unsigned long long *dst, const long long *src, size_t n)
 
 extern "C" int mceik_mcmc_cov_partials(mceik_mcmc *s, mceik_cov_partials *out)
 {
-    if (!s || !out || !s->cov) return 1;
-    McmcCov *p = s->cov;
+    if (!s || !out || !s->kept[KEPT_COV].state) return 1;
+    const McmcCov *p = (const McmcCov *)s->kept[KEPT_COV].state;
     if (!out->A || !out->S || !out->G || !out->Q || !out->C) return 1;
     const int within = p->V.within, ncold = temper_cold(s);
     if (within && (!out->PA || !out->P || !out->T)) return 1;
@@ -423,7 +379,7 @@ extern "C" int mceik_mcmc_cov_partials(mceik_mcmc *s, mceik_cov_partials *out)
     memcpy(out->kind, p->probes.kind, np * sizeof(int));
     memcpy(out->index, p->probes.index, np * sizeof(int));
     out->nchains = ncold;
-    out->nkept = p->n;
+    out->nkept = s->kept[KEPT_COV].n;
     return 0;
 }
 

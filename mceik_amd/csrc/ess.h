@@ -24,7 +24,7 @@
 // Q is unsigned.  P's increments b (2 Sc - b) and A's are negative where a
 // probe is (station statics): both are two's complement, as are the adds.
 // Per-chain arrays are indexed by the sampler's chain; a pipe's launch offsets
-// them (mcmc_ess_accumulate's chain_off).  The pooled words are shared: every
+// them (ess.hip ess_accumulate's chain_off).  The pooled words are shared: every
 // block adds atomically.
 struct EssDev {
     int nlevels, ncm, np, ne;
@@ -36,18 +36,5 @@ struct EssDev {
     unsigned long long *Q, *P;     // [nlevels][ne][2] (lo, hi): sum of B^2; sum over chains of Sc^2 at the last close
 };
 
-struct McmcEss;                    // a sampler's ESS state (ess.hip)
-
-// The kept-state hook's side (sampler.hip kept_queue), in posterior.h's
-// convention: the first n chains of view D / H / N, which are chains
-// [chain_off, chain_off + n) of the sampler, are added as kept state number t
-// of the chain, k = mcmc_ess_k(p) the trailing zero bits of t (it depends on
-// the count alone: the same for every pipe of a step); once every chain of a
-// kept step is queued, count the state.
-int mcmc_ess_k(const McmcEss *p);
-hipError_t mcmc_ess_accumulate(McmcEss *p, const McmcDev &D, const HypoDev &H, const NuisDev &N, int chain_off, int n,
-                               int k, hipStream_t st);
-void mcmc_ess_counted(McmcEss *p);
-long long mcmc_ess_count(const McmcEss *p);   // states accumulated per chain
-bool mcmc_ess_holds_nuis(const McmcEss *p);      // a static or noise-index probe is registered
-void mcmc_ess_free(McmcEss *p);
+// The batch-means sums' row of mceik_mcmc::kept (kept.h), off.
+KeptStream mcmc_ess_stream();

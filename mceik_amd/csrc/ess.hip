@@ -152,24 +152,29 @@ __global__ __launch_bounds__(256) void ess_accumulate_kernel(EssDev E, CovSrc R,
 struct McmcEss {
     EssDev E;                      // every chain of the sampler
     int nchains;
-    long long n;                   // states accumulated per chain
     ProbeList probes;
 };
 
-void mcmc_ess_counted(McmcEss *p) { p->n++; }
+enum { ESS_SC, ESS_PEND, ESS_A, ESS_Q, ESS_P, ESS_NARR };     // the arrays in the order of mceik_mcmc_ess_get / _set
 
-long long mcmc_ess_count(const McmcEss *p) { return p->n; }
-
-int mcmc_ess_k(const McmcEss *p) { return __builtin_ctzll((unsigned long long)(p->n + 1)); }
-
-bool mcmc_ess_holds_nuis(const McmcEss *p) { return probes_hold_nuis(p->probes); }
-
-void mcmc_ess_free(McmcEss *p)
+static int ess_arrays(void *state, KeptArray out[KEPT_MAX_ARRAYS])     // (pend: 4-byte words; none at one level)
 {
-    if (!p) return;
-    void *all[] = {p->probes.d, p->E.Sc, p->E.pend, p->E.A, p->E.Q, p->E.P};
-    for (void *q : all)
-        if (q) hipFree(q);
+    McmcEss *p = (McmcEss *)state;
+    const size_t ne = p->E.ne, nch = p->nchains, L = p->E.nlevels;
+    out[ESS_SC] = {(void **)&p->E.Sc, nch * ne * 8, 0};
+    out[ESS_PEND] = {(void **)&p->E.pend, (L - 1) * nch * ne * 4, 0};
+    out[ESS_A] = {(void **)&p->E.A, L * ne * 8, 0};
+    out[ESS_Q] = {(void **)&p->E.Q, 2 * L * ne * 8, 0};
+    out[ESS_P] = {(void **)&p->E.P, 2 * L * ne * 8, 0};
+    return ESS_NARR;
+}
+
+static bool ess_holds_nuis(const void *state) { return probes_hold_nuis(((const McmcEss *)state)->probes); }
+
+static void ess_free_extra(void *state)
+{
+    McmcEss *p = (McmcEss *)state;
+    if (p->probes.d) hipFree(p->probes.d);
     delete p;
 }
 
@@ -180,10 +185,15 @@ static void ess_launch(const EssDev &E, const CovSrc &R, int n, int k, int nl, h
     hipLaunchKernelGGL((ess_accumulate_kernel<NL, U>), grid, dim3(256), 0, st, E, R, n, k, nl);
 }
 
-hipError_t mcmc_ess_accumulate(McmcEss *p, const McmcDev &D, const HypoDev &H, const NuisDev &N, int chain_off, int n,
-                               int k, hipStream_t st)
+// The kept-state hook's side (kept.h KeptStream::accumulate): the chains are
+// added as kept state number t = count + 1 of the chain, k the trailing zero
+// bits of t.
+static hipError_t ess_accumulate(void *state, const McmcDev &D, const HypoDev &H, const NuisDev &N, int chain_off, int n,
+                                 long long count, hipStream_t st)
 {
+    const McmcEss *p = (const McmcEss *)state;
     if (n <= 0) return hipSuccess;
+    const int k = __builtin_ctzll((unsigned long long)(count + 1));
     EssDev E = p->E;
     E.Sc += (size_t)chain_off * E.ne;
     if (E.pend) E.pend += (size_t)chain_off * E.ne;
@@ -198,21 +208,16 @@ hipError_t mcmc_ess_accumulate(McmcEss *p, const McmcDev &D, const HypoDev &H, c
     return hipGetLastError();
 }
 
-// words (of 8 bytes; pend: of 4) of Sc, pend, A, Q, P
-static size_t ess_words(const McmcEss *p, int which)
+KeptStream mcmc_ess_stream()
 {
-    const size_t ne = p->E.ne, nch = p->nchains, L = p->E.nlevels;
-    const size_t w[5] = {nch * ne, (L - 1) * nch * ne, L * ne, 2 * L * ne, 2 * L * ne};
-    return w[which];
+    KeptStream k = {};
+    k.name = "the batch-means sums";
+    k.arrays = ess_arrays;
+    k.accumulate = ess_accumulate;
+    k.free_extra = ess_free_extra;
+    k.holds_nuis = ess_holds_nuis;
+    return k;
 }
-
-static void **ess_array(McmcEss *p, int which)
-{
-    void **a[5] = {(void **)&p->E.Sc, (void **)&p->E.pend, (void **)&p->E.A, (void **)&p->E.Q, (void **)&p->E.P};
-    return a[which];
-}
-
-static size_t ess_bytes(const McmcEss *p, int which) { return ess_words(p, which) * (which == 1 ? 4 : 8); }
 
 static bool ess_same(const McmcEss *p, const mceik_ess_opts *o)
 {
@@ -249,18 +254,11 @@ extern "C" int mceik_mcmc_ess_enable(mceik_mcmc *s, const mceik_ess_opts *o)
                             "fit its 32-bit word\n", xmax, o->nlevels);
         return 1;
     }
-    McmcEss *p = s->ess;
-    if (p && !ess_same(p, o) && p->n > 0) return 1;
-    if (p && ess_same(p, o)) {                      // the held sums go on
-        s->ess_on = true;
-        return 0;
-    }
+    KeptStream &ks = s->kept[KEPT_ESS];
+    const int rc = kept_enable_held(s, ks, ks.state && ess_same((const McmcEss *)ks.state, o), "mceik_mcmc_ess_enable");
+    if (rc != KEPT_REPLACE) return rc;
     DeviceScope dg(s->device);
-    HIPCHK(hipStreamSynchronize(s->stream));
-    s->ess = nullptr;
-    s->ess_on = false;
-    mcmc_ess_free(p);
-    p = new McmcEss();
+    McmcEss *p = new McmcEss();
     memset(p, 0, sizeof(*p));
     p->E.nlevels = o->nlevels;
     p->E.ncm = D.ncm;
@@ -268,99 +266,56 @@ extern "C" int mceik_mcmc_ess_enable(mceik_mcmc *s, const mceik_ess_opts *o)
     p->E.ne = D.ncm + o->np;
     p->E.pend_stride = (size_t)D.nchains * p->E.ne;
     p->nchains = D.nchains;
-    bool ok = probes_upload(p->probes, o->np, o->kind, o->index);
-    for (int a = 0; a < 5 && ok; a++) {
-        if (!ess_bytes(p, a)) continue;             // one level: no pend
-        ok = hipMalloc(ess_array(p, a), ess_bytes(p, a)) == hipSuccess &&
-             hipMemset(*ess_array(p, a), 0, ess_bytes(p, a)) == hipSuccess;
-    }
-    if (!ok) {
+    KeptArray a[KEPT_MAX_ARRAYS];
+    const int na = ess_arrays(p, a);
+    if (!probes_upload(p->probes, o->np, o->kind, o->index) || !kept_arrays_alloc(a, na)) {
         (void)hipGetLastError();
         fprintf(stderr, "mceik_mcmc_ess_enable: out of device memory (%zu B of accumulators)\n",
-                ess_bytes(p, 0) + ess_bytes(p, 1) + ess_bytes(p, 2) + ess_bytes(p, 3) + ess_bytes(p, 4));
-        mcmc_ess_free(p);
+                a[ESS_SC].bytes + a[ESS_PEND].bytes + a[ESS_A].bytes + a[ESS_Q].bytes + a[ESS_P].bytes);
+        kept_state_free(ks, p);
         return -1;
     }
     p->E.kind = p->probes.d;
     p->E.index = p->probes.d + o->np;
-    s->ess = p;
-    s->ess_on = true;
-    return 0;
+    return kept_publish(s, ks, p, "mceik_mcmc_ess_enable");
 }
 
-extern "C" int mceik_mcmc_ess_disable(mceik_mcmc *s)
-{
-    if (!s) return 1;
-    s->ess_on = false;                 // host state only: queued steps keep the kernels they were queued with
-    return 0;
-}
+extern "C" int mceik_mcmc_ess_disable(mceik_mcmc *s) { return s ? kept_disable(s, s->kept[KEPT_ESS]) : 1; }
 
-extern "C" int mceik_mcmc_ess_clear(mceik_mcmc *s)
-{
-    if (!s) return 1;
-    if (!s->ess) return 0;
-    DeviceScope dg(s->device);
-    const hipError_t e = hipStreamSynchronize(s->stream);
-    mcmc_ess_free(s->ess);
-    s->ess = nullptr;
-    s->ess_on = false;
-    return e == hipSuccess ? 0 : -1;
-}
+extern "C" int mceik_mcmc_ess_clear(mceik_mcmc *s) { return s ? kept_clear(s, s->kept[KEPT_ESS]) : 1; }
 
-extern "C" int mceik_mcmc_ess_accumulate(mceik_mcmc *s)
-{
-    if (!s || !s->ess || !s->ess_on) return 1;
-    DeviceScope dg(s->device);
-    // tempering: the cold chains
-    HIPCHK(mcmc_ess_accumulate(s->ess, s->D, s->H, s->N, 0, temper_cold(s), mcmc_ess_k(s->ess), s->stream));
-    mcmc_ess_counted(s->ess);
-    return 0;
-}
+extern "C" int mceik_mcmc_ess_accumulate(mceik_mcmc *s) { return s ? kept_accumulate(s, s->kept[KEPT_ESS]) : 1; }
 
 extern "C" int mceik_mcmc_ess_get(mceik_mcmc *s, long long *n, long long *Sc, int *pend, long long *A,
                                   unsigned long long *Q, unsigned long long *P)
 {
-    if (!s || !s->ess) return 1;
-    McmcEss *p = s->ess;
-    if (mceik_mcmc_sync(s)) return -1;
-    DeviceScope dg(s->device);
-    if (n) *n = p->n;
-    void *dst[5] = {Sc, pend, A, Q, P};
-    for (int a = 0; a < 5; a++)
-        if (dst[a] && ess_bytes(p, a)) HIPCHK(hipMemcpy(dst[a], *ess_array(p, a), ess_bytes(p, a), hipMemcpyDeviceToHost));
-    return 0;
+    void *const host[] = {Sc, pend, A, Q, P};
+    return s ? kept_get(s, s->kept[KEPT_ESS], n, host) : 1;
 }
 
 extern "C" int mceik_mcmc_ess_set(mceik_mcmc *s, long long n, const long long *Sc, const int *pend, const long long *A,
                                   const unsigned long long *Q, const unsigned long long *P)
 {
-    if (!s || !s->ess || n < 0) return 1;
-    McmcEss *p = s->ess;
-    const void *src[5] = {Sc, pend, A, Q, P};
-    for (int a = 0; a < 5; a++)
-        if (!src[a] && ess_bytes(p, a)) return 1;
-    DeviceScope dg(s->device);
-    HIPCHK(hipStreamSynchronize(s->stream));
-    for (int a = 0; a < 5; a++)
-        if (ess_bytes(p, a)) HIPCHK(hipMemcpy(*ess_array(p, a), src[a], ess_bytes(p, a), hipMemcpyHostToDevice));
-    p->n = n;
-    return 0;
+    const void *const host[] = {Sc, pend, A, Q, P};
+    return s ? kept_set(s, s->kept[KEPT_ESS], n, host) : 1;
 }
 
 extern "C" int mceik_mcmc_ess_partials(mceik_mcmc *s, mceik_ess_partials *out)
 {
-    if (!s || !out || !s->ess || !out->A || !out->Q || !out->P) return 1;
-    McmcEss *p = s->ess;
+    if (!s || !out || !s->kept[KEPT_ESS].state || !out->A || !out->Q || !out->P) return 1;
+    McmcEss *p = (McmcEss *)s->kept[KEPT_ESS].state;
     if (mceik_mcmc_sync(s)) return -1;
     DeviceScope dg(s->device);
-    HIPCHK(hipMemcpy(out->A, p->E.A, ess_bytes(p, 2), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out->Q, p->E.Q, ess_bytes(p, 3), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out->P, p->E.P, ess_bytes(p, 4), hipMemcpyDeviceToHost));
+    KeptArray a[KEPT_MAX_ARRAYS];
+    ess_arrays(p, a);
+    HIPCHK(hipMemcpy(out->A, p->E.A, a[ESS_A].bytes, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out->Q, p->E.Q, a[ESS_Q].bytes, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out->P, p->E.P, a[ESS_P].bytes, hipMemcpyDeviceToHost));
     out->ncm = p->E.ncm;
     out->np = p->E.np;
     out->nlevels = p->E.nlevels;
     out->nchains = temper_cold(s);
-    out->nkept = p->n;
+    out->nkept = s->kept[KEPT_ESS].n;
     return 0;
 }
 

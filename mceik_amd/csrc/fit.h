@@ -6,6 +6,7 @@
 
 #include "../../include/mceik.h"
 #include "hypo.h"
+#include "kept.h"
 #include "mcmc_common.h"
 #include "nuis.h"
 
@@ -18,7 +19,7 @@
 // Wrap bounds: |q| < 2^31, so an int64 sum holds 2^32 states (over all chains)
 // and a 128-bit sum of squares never wraps before it.
 // The scratch rows are indexed by the sampler's chain; a pipe's launch offsets
-// them (mcmc_fit_accumulate's chain_off).  The pooled words are shared: every
+// them (fit.hip fit_accumulate's chain_off).  The pooled words are shared: every
 // block adds atomically.
 struct FitDev {
     int nobs, nev, nbins;
@@ -35,15 +36,6 @@ struct FitDev {
     unsigned long long *sat;       // [3] clamped q, zq, tq
 };
 
-struct McmcFit;                    // a sampler's data-fit state (fit.hip)
-
-// The kept-state hook's side (sampler.hip kept_queue), in posterior.h's
-// convention: the first n chains of view D / H / N, which are chains
-// [chain_off, chain_off + n) of the sampler, are added; once every chain of a
-// kept step is queued, count the state.  D.ttab_cur holds the chains' current
-// tables (at the chains' own event nodes: H is not read).
-hipError_t mcmc_fit_accumulate(McmcFit *p, const McmcDev &D, const HypoDev &H, const NuisDev &N, int chain_off, int n,
-                               hipStream_t st);
-void mcmc_fit_counted(McmcFit *p);
-long long mcmc_fit_count(const McmcFit *p);   // states accumulated per chain
-void mcmc_fit_free(McmcFit *p);
+// The data-fit sums' row of mceik_mcmc::kept (kept.h), off; it is the one that
+// makes a one-model sampler hold its current tables while on.
+KeptStream mcmc_fit_stream();

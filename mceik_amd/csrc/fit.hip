@@ -165,48 +165,38 @@ __global__ __launch_bounds__(FIT_LANES) void fit_reduce_kernel(FitDev F, const i
 struct McmcFit {
     FitDev F;                      // every chain of the sampler
     int nchains, nphase, nstat;
-    long long n;                   // states accumulated per chain
     double tick, zmax;
     std::vector<double> t0_ref;    // [nev]
     double *d_t0_ref;
 };
 
-void mcmc_fit_counted(McmcFit *p) { p->n++; }
-
-long long mcmc_fit_count(const McmcFit *p) { return p->n; }
-
-static void **fit_array(McmcFit *p, int which)
+// sq, szq, sq2, szq2, stq, stq2, hist, sat: words of 8 bytes, 16 bytes of slack each
+static int fit_arrays(void *state, KeptArray out[KEPT_MAX_ARRAYS])
 {
+    McmcFit *p = (McmcFit *)state;
+    const size_t no = p->F.nobs, ne = p->F.nev;
     void **a[FIT_NARR] = {(void **)&p->F.sq,  (void **)&p->F.szq,  (void **)&p->F.sq2,  (void **)&p->F.szq2,
                           (void **)&p->F.stq, (void **)&p->F.stq2, (void **)&p->F.hist, (void **)&p->F.sat};
-    return a[which];
-}
-
-// words of 8 bytes of sq, szq, sq2, szq2, stq, stq2, hist, sat
-static size_t fit_words(const McmcFit *p, int which)
-{
-    const size_t no = p->F.nobs, ne = p->F.nev;
     const size_t w[FIT_NARR] = {no, no, 2 * no, 2 * no, ne, 2 * ne, (size_t)p->nphase * p->nstat * p->F.nbins, 3};
-    return w[which];
+    for (int k = 0; k < FIT_NARR; k++) out[k] = {a[k], w[k] * 8, 16};
+    return FIT_NARR;
 }
 
-static size_t fit_bytes(const McmcFit *p, int which) { return fit_words(p, which) * 8; }
-
-void mcmc_fit_free(McmcFit *p)
+static void fit_free_extra(void *state)
 {
-    if (!p) return;
+    McmcFit *p = (McmcFit *)state;
     void *all[] = {p->F.q, p->F.zq, p->F.bin, p->F.tq, p->d_t0_ref};
     for (void *q : all)
         if (q) hipFree(q);
-    for (int a = 0; a < FIT_NARR; a++)
-        if (*fit_array(p, a)) hipFree(*fit_array(p, a));
     delete p;
 }
 
-hipError_t mcmc_fit_accumulate(McmcFit *p, const McmcDev &D, const HypoDev &H, const NuisDev &N, int chain_off, int n,
-                               hipStream_t st)
+// The kept-state hook's side (kept.h KeptStream::accumulate).  D.ttab_cur holds
+// the chains' current tables (at the chains' own event nodes: H is not read).
+static hipError_t fit_accumulate(void *state, const McmcDev &D, const HypoDev &, const NuisDev &N, int chain_off, int n,
+                                 long long, hipStream_t st)
 {
-    (void)H;
+    const McmcFit *p = (const McmcFit *)state;
     if (n <= 0) return hipSuccess;
     if (!D.ttab_cur) return hipErrorInvalidValue;    // (enable makes a one-model sampler hold its current tables)
     FitDev F = p->F;
@@ -221,6 +211,17 @@ hipError_t mcmc_fit_accumulate(McmcFit *p, const McmcDev &D, const HypoDev &H, c
     hipLaunchKernelGGL(fit_reduce_kernel, grid, dim3(FIT_LANES), (size_t)F.nbins * FIT_LANES * sizeof(unsigned), st, F,
                        D.obs_stat, D.obs_phase, D.obs_mask, D.obs_ptr, D.nstat, n, nbp);
     return hipGetLastError();
+}
+
+KeptStream mcmc_fit_stream()
+{
+    KeptStream k = {};
+    k.name = "the data-fit sums";
+    k.needs_tables1 = true;
+    k.arrays = fit_arrays;
+    k.accumulate = fit_accumulate;
+    k.free_extra = fit_free_extra;
+    return k;
 }
 
 // tick = 2^k, k in [-64, 64]
@@ -257,18 +258,11 @@ extern "C" int mceik_mcmc_fit_enable(mceik_mcmc *s, const mceik_fit_opts *o)
     const int nobs = (int)s->h_ostat.size(), nev = D.nev;
     for (int e = 0; e < nev && o->t0_ref; e++)
         if (!(fabs(o->t0_ref[e]) <= 1e300)) return 1;
-    McmcFit *p = s->fit;
-    if (p && !fit_same(p, o) && p->n > 0) return 1;
-    if (p && fit_same(p, o)) {                      // the held sums go on
-        s->fit_on = true;
-        return mcmc_tables1_hold(s, "mceik_mcmc_fit_enable");
-    }
+    KeptStream &k = s->kept[KEPT_FIT];
+    const int rc = kept_enable_held(s, k, k.state && fit_same((const McmcFit *)k.state, o), "mceik_mcmc_fit_enable");
+    if (rc != KEPT_REPLACE) return rc;
     DeviceScope dg(s->device);
-    HIPCHK(hipStreamSynchronize(s->stream));
-    s->fit = nullptr;
-    s->fit_on = false;
-    mcmc_fit_free(p);
-    p = new McmcFit();
+    McmcFit *p = new McmcFit();
     p->F.nobs = nobs;
     p->F.nev = nev;
     p->F.nbins = o->nbins;
@@ -283,94 +277,50 @@ extern "C" int mceik_mcmc_fit_enable(mceik_mcmc *s, const mceik_fit_opts *o)
     p->t0_ref.assign((size_t)nev, 0.0);
     if (o->t0_ref) p->t0_ref.assign(o->t0_ref, o->t0_ref + nev);
     const size_t nch = (size_t)D.nchains, no = nobs > 0 ? nobs : 1;
-    auto zalloc = [](void **q, size_t bytes) {
-        return hipMalloc(q, bytes) == hipSuccess && hipMemset(*q, 0, bytes) == hipSuccess;
-    };
-    bool ok = zalloc((void **)&p->F.q, nch * no * 4) && zalloc((void **)&p->F.zq, nch * no * 4) &&
-              zalloc((void **)&p->F.bin, nch * no * 4) && zalloc((void **)&p->F.tq, nch * nev * 4) &&
-              zalloc((void **)&p->d_t0_ref, (size_t)nev * 8);
-    for (int a = 0; a < FIT_NARR && ok; a++) ok = zalloc(fit_array(p, a), fit_bytes(p, a) + 16);
-    ok = ok && hipMemcpy(p->d_t0_ref, p->t0_ref.data(), (size_t)nev * 8, hipMemcpyHostToDevice) == hipSuccess;
+    KeptArray a[KEPT_MAX_ARRAYS], rows[5] = {{(void **)&p->F.q, nch * no * 4, 0},
+                                             {(void **)&p->F.zq, nch * no * 4, 0},
+                                             {(void **)&p->F.bin, nch * no * 4, 0},
+                                             {(void **)&p->F.tq, nch * nev * 4, 0},
+                                             {(void **)&p->d_t0_ref, (size_t)nev * 8, 0}};
+    const bool ok = kept_arrays_alloc(rows, 5) && kept_arrays_alloc(a, fit_arrays(p, a)) &&
+                    hipMemcpy(p->d_t0_ref, p->t0_ref.data(), (size_t)nev * 8, hipMemcpyHostToDevice) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
         fprintf(stderr, "mceik_mcmc_fit_enable: out of device memory (%zu B of scratch rows)\n",
                 nch * (3 * no + nev) * 4);
-        mcmc_fit_free(p);
+        kept_state_free(k, p);
         return -1;
     }
     p->F.t0_ref = p->d_t0_ref;
-    s->fit = p;
-    s->fit_on = true;
-    return mcmc_tables1_hold(s, "mceik_mcmc_fit_enable");
+    return kept_publish(s, k, p, "mceik_mcmc_fit_enable");
 }
 
-extern "C" int mceik_mcmc_fit_disable(mceik_mcmc *s)
-{
-    if (!s) return 1;
-    if (!s->fit_on) return 0;
-    s->fit_on = false;
-    return mcmc_tables1_drop(s);       // (a one-model sampler stops holding its current tables unless nuisance state needs them)
-}
+extern "C" int mceik_mcmc_fit_disable(mceik_mcmc *s) { return s ? kept_disable(s, s->kept[KEPT_FIT]) : 1; }
 
-extern "C" int mceik_mcmc_fit_clear(mceik_mcmc *s)
-{
-    if (!s) return 1;
-    if (!s->fit) return 0;
-    DeviceScope dg(s->device);
-    const hipError_t e = hipStreamSynchronize(s->stream);
-    mcmc_fit_free(s->fit);
-    s->fit = nullptr;
-    s->fit_on = false;
-    const int rc = mcmc_tables1_drop(s);
-    return e == hipSuccess ? rc : -1;
-}
+extern "C" int mceik_mcmc_fit_clear(mceik_mcmc *s) { return s ? kept_clear(s, s->kept[KEPT_FIT]) : 1; }
 
-extern "C" int mceik_mcmc_fit_accumulate(mceik_mcmc *s)
-{
-    if (!s || !s->fit || !s->fit_on) return 1;
-    DeviceScope dg(s->device);
-    // tempering: the cold chains
-    HIPCHK(mcmc_fit_accumulate(s->fit, s->D, s->H, s->N, 0, temper_cold(s), s->stream));
-    mcmc_fit_counted(s->fit);
-    return 0;
-}
+extern "C" int mceik_mcmc_fit_accumulate(mceik_mcmc *s) { return s ? kept_accumulate(s, s->kept[KEPT_FIT]) : 1; }
 
 extern "C" int mceik_mcmc_fit_get(mceik_mcmc *s, long long *n, long long *sq, long long *szq, unsigned long long *sq2,
                                   unsigned long long *szq2, long long *stq, unsigned long long *stq2, long long *hist,
                                   long long *sat)
 {
-    if (!s || !s->fit) return 1;
-    McmcFit *p = s->fit;
-    if (mceik_mcmc_sync(s)) return -1;
-    DeviceScope dg(s->device);
-    if (n) *n = p->n;
-    void *dst[FIT_NARR] = {sq, szq, sq2, szq2, stq, stq2, hist, sat};
-    for (int a = 0; a < FIT_NARR; a++)
-        if (dst[a] && fit_bytes(p, a)) HIPCHK(hipMemcpy(dst[a], *fit_array(p, a), fit_bytes(p, a), hipMemcpyDeviceToHost));
-    return 0;
+    void *const host[] = {sq, szq, sq2, szq2, stq, stq2, hist, sat};
+    return s ? kept_get(s, s->kept[KEPT_FIT], n, host) : 1;
 }
 
 extern "C" int mceik_mcmc_fit_set(mceik_mcmc *s, long long n, const long long *sq, const long long *szq,
                                   const unsigned long long *sq2, const unsigned long long *szq2, const long long *stq,
                                   const unsigned long long *stq2, const long long *hist, const long long *sat)
 {
-    if (!s || !s->fit || n < 0) return 1;
-    McmcFit *p = s->fit;
-    const void *src[FIT_NARR] = {sq, szq, sq2, szq2, stq, stq2, hist, sat};
-    for (int a = 0; a < FIT_NARR; a++)
-        if (!src[a] && fit_bytes(p, a)) return 1;
-    DeviceScope dg(s->device);
-    HIPCHK(hipStreamSynchronize(s->stream));
-    for (int a = 0; a < FIT_NARR; a++)
-        if (fit_bytes(p, a)) HIPCHK(hipMemcpy(*fit_array(p, a), src[a], fit_bytes(p, a), hipMemcpyHostToDevice));
-    p->n = n;
-    return 0;
+    const void *const host[] = {sq, szq, sq2, szq2, stq, stq2, hist, sat};
+    return s ? kept_set(s, s->kept[KEPT_FIT], n, host) : 1;
 }
 
 extern "C" int mceik_mcmc_fit_last(mceik_mcmc *s, int *q, int *zq, int *tq)
 {
-    if (!s || !s->fit) return 1;
-    McmcFit *p = s->fit;
+    if (!s || !s->kept[KEPT_FIT].state) return 1;
+    const McmcFit *p = (const McmcFit *)s->kept[KEPT_FIT].state;
     if (mceik_mcmc_sync(s)) return -1;
     DeviceScope dg(s->device);
     const size_t nch = (size_t)p->nchains;
@@ -390,14 +340,14 @@ static bool fit_parts_ok(const mceik_fit_partials *p)
 
 extern "C" int mceik_mcmc_fit_partials(mceik_mcmc *s, mceik_fit_partials *out)
 {
-    if (!s || !out || !s->fit) return 1;
-    McmcFit *p = s->fit;
+    if (!s || !out || !s->kept[KEPT_FIT].state) return 1;
+    const McmcFit *p = (const McmcFit *)s->kept[KEPT_FIT].state;
     out->nobs = p->F.nobs; out->nev = p->F.nev; out->nphase = p->nphase; out->nstat = p->nstat; out->nbins = p->F.nbins;
     if (!fit_parts_ok(out)) return 1;
     out->tick = p->tick;
     out->zmax = p->zmax;
     out->nchains = temper_cold(s);
-    out->nkept = p->n;
+    out->nkept = s->kept[KEPT_FIT].n;
     if (mceik_mcmc_fit_get(s, nullptr, out->sq, out->szq, out->sq2, out->szq2, out->stq, out->stq2, out->hist, out->sat))
         return -1;
     DeviceScope dg(s->device);

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "kept.h"
 #include "mcmc_common.h"
 
 #define MCEIK_POST_MAX_BINS 128
@@ -16,13 +17,7 @@ struct PostDev {
     unsigned *hist;                // [ncm][nbins] pooled over chains
 };
 
-struct McmcPost;                   // a sampler's posterior state (posterior.hip)
-
-// The kept-state hook's side (sampler.hip kept_queue): add the current models
-// of the first n chains of view D, which are chains [chain_off, chain_off + n)
-// of the sampler, on stream st; once every chain of a kept step is queued,
-// count the state.  cov.h and ess.h take their chains the same way.
-hipError_t mcmc_post_accumulate(McmcPost *p, const McmcDev &D, int chain_off, int n, hipStream_t st);
-void mcmc_post_counted(McmcPost *p);
-long long mcmc_post_count(const McmcPost *p);   // states accumulated per chain
-void mcmc_post_free(McmcPost *p);
+// The posterior's row of mceik_mcmc::kept (kept.h), off: the kept-state hook
+// (sampler.hip kept_queue) and the lifecycle (sampler_api.hip) reach
+// posterior.hip through it.
+KeptStream mcmc_post_stream();

@@ -157,31 +157,37 @@ __global__ __launch_bounds__(64) void post_reduce_kernel(PostDev A, int nchains,
 struct McmcPost {
     PostDev P;
     int nchains, ncm;
-    long long n;                   // states accumulated per chain
     long long *d_S;                // partials scratch [ncm], [ncm][2], [ncm][2]
     unsigned long long *d_Q, *d_P;
 };
 
 static size_t post_rows(const McmcPost *p) { return p->P.per_chain ? (size_t)p->nchains : 1; }
 
-void mcmc_post_free(McmcPost *p)
+static int post_arrays(void *state, KeptArray out[KEPT_MAX_ARRAYS])     // sum, sumsq, hist (4-byte words; none at nbins = 0)
 {
-    if (!p) return;
-    if (p->P.sum) hipFree(p->P.sum);
-    if (p->P.sumsq) hipFree(p->P.sumsq);
-    if (p->P.hist) hipFree(p->P.hist);
+    McmcPost *p = (McmcPost *)state;
+    const size_t m = post_rows(p) * p->ncm * 8;
+    out[0] = {(void **)&p->P.sum, m, 0};
+    out[1] = {(void **)&p->P.sumsq, m, 0};
+    out[2] = {(void **)&p->P.hist, (size_t)p->ncm * p->P.nbins * 4, 0};
+    return 3;
+}
+
+static void post_free_extra(void *state)
+{
+    McmcPost *p = (McmcPost *)state;
     if (p->d_S) hipFree(p->d_S);
     if (p->d_Q) hipFree(p->d_Q);
     if (p->d_P) hipFree(p->d_P);
     delete p;
 }
 
-void mcmc_post_counted(McmcPost *p) { p->n++; }
-
-long long mcmc_post_count(const McmcPost *p) { return p->n; }
-
-hipError_t mcmc_post_accumulate(McmcPost *p, const McmcDev &D, int chain_off, int n, hipStream_t st)
+// The kept-state hook's side (kept.h KeptStream::accumulate): add the current
+// models of the first n chains of view D.
+static hipError_t post_accumulate(void *state, const McmcDev &D, const HypoDev &, const NuisDev &, int chain_off, int n,
+                                  long long, hipStream_t st)
 {
+    const McmcPost *p = (const McmcPost *)state;
     if (n <= 0) return hipSuccess;
     McmcDev V = D;                     // the kernel adds every chain of the view it is given
     V.nchains = n;
@@ -200,28 +206,31 @@ hipError_t mcmc_post_accumulate(McmcPost *p, const McmcDev &D, int chain_off, in
     return hipGetLastError();
 }
 
-static int post_zero(McmcPost *p, hipStream_t st)
+KeptStream mcmc_post_stream()
 {
-    const size_t n = post_rows(p) * p->ncm;
-    HIPCHK(hipMemsetAsync(p->P.sum, 0, n * 8, st));
-    HIPCHK(hipMemsetAsync(p->P.sumsq, 0, n * 8, st));
-    if (p->P.hist) HIPCHK(hipMemsetAsync(p->P.hist, 0, (size_t)p->ncm * p->P.nbins * 4, st));
-    p->n = 0;
-    return 0;
+    KeptStream k = {};
+    k.name = "the streaming posterior";
+    k.arrays = post_arrays;
+    k.accumulate = post_accumulate;
+    k.free_extra = post_free_extra;
+    return k;
 }
 
+// The posterior has no disabled state that keeps its sums: enabling always
+// starts from zero (other options: from new arrays), disabling drops it.
 extern "C" int mceik_mcmc_posterior_enable(mceik_mcmc *s, const mceik_posterior_opts *o)
 {
     if (!s || !o) return 1;
     if (o->nbins < 0 || o->nbins > MCEIK_POST_MAX_BINS) return 1;
     DeviceScope dg(s->device);
     const int per_chain = o->per_chain ? 1 : 0;
-    McmcPost *p = s->post;
+    KeptStream &k = s->kept[KEPT_POST];
+    McmcPost *p = (McmcPost *)k.state;
     if (p && (p->P.per_chain != per_chain || p->P.nbins != o->nbins)) {
-        HIPCHK(hipStreamSynchronize(s->stream));
-        mcmc_post_free(p);
-        s->post = p = nullptr;
+        if (kept_clear(s, k)) return -1;
+        p = nullptr;
     }
+    KeptArray a[KEPT_MAX_ARRAYS];
     if (!p) {
         p = new McmcPost();
         memset(p, 0, sizeof(*p));
@@ -229,80 +238,47 @@ extern "C" int mceik_mcmc_posterior_enable(mceik_mcmc *s, const mceik_posterior_
         p->P.nbins = o->nbins;
         p->nchains = s->D.nchains;
         p->ncm = s->D.ncm;
-        const size_t n = post_rows(p) * p->ncm, m = (size_t)p->ncm;
-        if (hipMalloc((void **)&p->P.sum, n * 8) != hipSuccess || hipMalloc((void **)&p->P.sumsq, n * 8) != hipSuccess ||
-            (o->nbins && hipMalloc((void **)&p->P.hist, m * o->nbins * 4) != hipSuccess) ||
-            hipMalloc((void **)&p->d_S, m * 8) != hipSuccess || hipMalloc((void **)&p->d_Q, m * 16) != hipSuccess ||
-            hipMalloc((void **)&p->d_P, m * 16) != hipSuccess) {
+        const size_t m = (size_t)p->ncm;
+        if (!kept_arrays_alloc(a, post_arrays(p, a)) || hipMalloc((void **)&p->d_S, m * 8) != hipSuccess ||
+            hipMalloc((void **)&p->d_Q, m * 16) != hipSuccess || hipMalloc((void **)&p->d_P, m * 16) != hipSuccess) {
             (void)hipGetLastError();
-            fprintf(stderr, "mceik_mcmc_posterior_enable: out of device memory (%zu B of moments)\n", 2 * n * 8);
-            mcmc_post_free(p);
+            fprintf(stderr, "mceik_mcmc_posterior_enable: out of device memory (%zu B of moments)\n",
+                    2 * post_rows(p) * m * 8);
+            kept_state_free(k, p);
             return -1;
         }
+        kept_publish(s, k, p, "mceik_mcmc_posterior_enable");
     }
-    if (post_zero(p, s->stream)) {
-        mcmc_post_free(p);
-        s->post = nullptr;
+    if (kept_arrays_zero(a, post_arrays(p, a), s->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        kept_clear(s, k);
         return -1;
     }
-    s->post = p;
+    k.n = 0;
     return 0;
 }
 
-extern "C" int mceik_mcmc_posterior_disable(mceik_mcmc *s)
-{
-    if (!s) return 1;
-    if (!s->post) return 0;
-    DeviceScope dg(s->device);
-    const hipError_t e = hipStreamSynchronize(s->stream);
-    mcmc_post_free(s->post);
-    s->post = nullptr;
-    return e == hipSuccess ? 0 : -1;
-}
+extern "C" int mceik_mcmc_posterior_disable(mceik_mcmc *s) { return s ? kept_clear(s, s->kept[KEPT_POST]) : 1; }
 
-extern "C" int mceik_mcmc_posterior_accumulate(mceik_mcmc *s)
-{
-    if (!s || !s->post) return 1;
-    DeviceScope dg(s->device);
-    HIPCHK(mcmc_post_accumulate(s->post, s->D, 0, temper_cold(s), s->stream));   // tempering: the hot chains' rows stay zero
-    mcmc_post_counted(s->post);
-    return 0;
-}
+extern "C" int mceik_mcmc_posterior_accumulate(mceik_mcmc *s) { return s ? kept_accumulate(s, s->kept[KEPT_POST]) : 1; }
 
 extern "C" int mceik_mcmc_posterior_get(mceik_mcmc *s, long long *n, long long *sum, long long *sumsq, unsigned *hist)
 {
-    if (!s || !s->post) return 1;
-    const McmcPost *p = s->post;
-    if (mceik_mcmc_sync(s)) return -1;
-    DeviceScope dg(s->device);
-    const size_t m = post_rows(p) * p->ncm;
-    if (n) *n = p->n;
-    if (sum) HIPCHK(hipMemcpy(sum, p->P.sum, m * 8, hipMemcpyDeviceToHost));
-    if (sumsq) HIPCHK(hipMemcpy(sumsq, p->P.sumsq, m * 8, hipMemcpyDeviceToHost));
-    if (hist && p->P.nbins) HIPCHK(hipMemcpy(hist, p->P.hist, (size_t)p->ncm * p->P.nbins * 4, hipMemcpyDeviceToHost));
-    return 0;
+    void *const host[] = {sum, sumsq, hist};
+    return s ? kept_get(s, s->kept[KEPT_POST], n, host) : 1;
 }
 
 extern "C" int mceik_mcmc_posterior_set(mceik_mcmc *s, long long n, const long long *sum, const long long *sumsq,
                                         const unsigned *hist)
 {
-    if (!s || !s->post) return 1;
-    McmcPost *p = s->post;
-    if (n < 0 || !sum || !sumsq || (p->P.nbins && !hist)) return 1;
-    DeviceScope dg(s->device);
-    const size_t m = post_rows(p) * p->ncm;
-    HIPCHK(hipStreamSynchronize(s->stream));
-    HIPCHK(hipMemcpy(p->P.sum, sum, m * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(p->P.sumsq, sumsq, m * 8, hipMemcpyHostToDevice));
-    if (p->P.nbins) HIPCHK(hipMemcpy(p->P.hist, hist, (size_t)p->ncm * p->P.nbins * 4, hipMemcpyHostToDevice));
-    p->n = n;
-    return 0;
+    const void *const host[] = {sum, sumsq, hist};
+    return s ? kept_set(s, s->kept[KEPT_POST], n, host) : 1;
 }
 
 extern "C" int mceik_mcmc_posterior_partials(mceik_mcmc *s, mceik_posterior_partials *out)
 {
-    if (!s || !out || !s->post) return 1;
-    const McmcPost *p = s->post;
+    if (!s || !out || !s->kept[KEPT_POST].state) return 1;
+    const McmcPost *p = (const McmcPost *)s->kept[KEPT_POST].state;
     if (!out->S || !out->Q || !out->P || (p->P.nbins && !out->hist)) return 1;
     const int ncm = p->ncm, ncold = temper_cold(s);
     {
@@ -326,7 +302,7 @@ extern "C" int mceik_mcmc_posterior_partials(mceik_mcmc *s, mceik_posterior_part
     out->nbins = p->P.nbins;
     out->per_chain = p->P.per_chain;
     out->nchains = ncold;
-    out->nkept = p->n;
+    out->nkept = s->kept[KEPT_POST].n;
     return 0;
 }
 

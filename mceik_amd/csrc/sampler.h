@@ -1,6 +1,8 @@
 // sampler.h -- the per-GPU MCMC sampler's host state (include/mceik.h
-// mceik_mcmc; not public), shared by sampler.hip (init, pipes, step loop,
-// finalize) and sampler_api.hip (accessors, tempering and block entry points).
+// mceik_mcmc; not public), shared by sampler.hip (init, pipes, step plan, step
+// loop, kept-state hook, finalize), sampler_api.hip (accessors, the entry
+// points of the moves, the lifecycle of the kept-state accumulators) and the
+// feature files that keep their state in it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -15,6 +17,7 @@
 #include "fit.h"
 #include "fsm_common.h"
 #include "hypo.h"
+#include "kept.h"
 #include "lang.h"
 #include "nuis.h"
 #include "posterior.h"
@@ -27,9 +30,9 @@
 
 // A pipe: a part of the chains stepped on a stream of its own.  D, B, P, H, N, L, De, V, fb
 // and fb_hyp are views of the sampler's restricted to the pipe's chains;
-// pipes_refresh alone writes them.  (The accumulators of kept states --
-// posterior, covariances, batch means, data fit -- have no views: their
-// accumulate calls take the pipe's chain offset.)
+// pipes_refresh alone writes them.  (The accumulators of kept states,
+// mceik_mcmc::kept, have no views: a KeptStream's accumulate takes the pipe's
+// chain offset.)
 struct Pipe {
     McmcDev D;
     BlockDev B;
@@ -85,7 +88,15 @@ struct mceik_mcmc {
     int device, max_samples, nburn, keepk, nkept, niter_total;
     int nkept_base;                    // nkept at the last restore: earlier states are not in the ring
     long long step;
-    McmcPost *post;                    // streaming posterior accumulators (posterior.hip), or null
+    // The accumulators of kept states (kept.h): the streaming
+    // posterior (s.10), the probe-to-cell covariances (s.16), the batch-means
+    // sums (s.19) and the data-fit sums (s.20); all off by default.  While one
+    // is on, a multi-step launch ends right after the next kept step.  The
+    // posterior is on whenever it has state; the others keep their sums over a
+    // disable.  While the data-fit sums are on, a one-model sampler holds its
+    // current tables (D.ttab_cur = ttab_cur1, as with nuisance state) and takes
+    // the per-step branch, whose accept copies them.
+    KeptStream kept[KEPT_NSTREAM];
     // Parallel tempering (temper.hip); ntemps = 0: off.  Rung r
     // of replica group g is chain r * G + g (G = nchains / ntemps), so the cold
     // chains are [0, G).  plan_step (sampler.hip) says which steps a swap round
@@ -134,29 +145,9 @@ struct mceik_mcmc {
     NuisDev N;
     NuisDev Nbuf;                      // the arrays of the first enable, kept across clear
     int nuis_cap_sub, nuis_cap_nk;     // sub-moves / ladder entries the arrays hold
-    float *ttab_cur1;                  // one model: [nchains][nstat][nev] current tables while N.kn is set or fit_on
+    float *ttab_cur1;                  // one model: [nchains][nstat][nev] current tables while N.kn is set or the data-fit sums are on
     long long nuis_n;                  // states in the moments (cold chains x kept steps)
     std::vector<int> h_ostat, h_omask, h_ophase;   // [nobs] the observations' station, mask and phase (host copies)
-    // Probe-to-cell covariances (cov.hip); off by default.  cov is
-    // null until an enable and again after a clear; cov_on: kept steps add to it
-    // (a disable keeps the sums).  While on, a multi-step launch ends right
-    // after the next kept step, as it does for the posterior.
-    McmcCov *cov;
-    bool cov_on;
-    // Effective sample sizes by batch means (ess.hip); off by
-    // default.  ess is null until an enable and again after a clear; ess_on:
-    // kept steps add to it (a disable keeps the sums).  While on, a multi-step
-    // launch ends right after the next kept step, as it does for the posterior.
-    McmcEss *ess;
-    bool ess_on;
-    // Pick residuals, origin times and data-fit checks (fit.hip);
-    // off by default.  fit is null until an enable and again after a clear;
-    // fit_on: kept steps add to it (a disable keeps the sums).  While on, a
-    // multi-step launch ends right after the next kept step, and a one-model
-    // sampler holds its current tables (D.ttab_cur = ttab_cur1, as with nuisance
-    // state) and takes the per-step branch, whose accept copies them.
-    McmcFit *fit;
-    bool fit_on;
     // Discrete Langevin moves (lang.hip); off by default.  L's
     // arrays are null until the first enable, which allocates everything a step
     // uses: the per-chain arrays, and per pipe (lang_pipe) the fields, the
@@ -235,10 +226,16 @@ int temper_round(mceik_mcmc *s, int parity);
 // data-fit sums of a one-model sampler (they read the chains' current tables,
 // which the multi-step kernel's epilogue keeps for two models only); the L1
 // likelihood (the multi-step kernel's epilogue evaluates the L2 misfit only).
+static inline bool kept_needs_tables1(const mceik_mcmc *s)     // an accumulator that reads the current tables is on
+{
+    for (const KeptStream &k : s->kept)
+        if (k.on && k.needs_tables1) return true;
+    return false;
+}
 static inline bool mcmc_multi_step(const mceik_mcmc *s)
 {
     return s->persist && !s->block_on && !s->prior_on && !s->hypo_on && !s->N.kn && !s->lang_on && !s->de_on && !s->vor_on &&
-           !(s->fit_on && s->D.nphase == 1) && !s->D.l1;
+           !(kept_needs_tables1(s) && s->D.nphase == 1) && !s->D.l1;
 }
 // A one-model sampler's current tables (sampler_api.hip).  hold: while nuisance
 // state is held or the data-fit sums are on, D.ttab_cur = ttab_cur1 (allocated
@@ -247,6 +244,23 @@ static inline bool mcmc_multi_step(const mceik_mcmc *s)
 // them, the sampler is the plain one again.  Both synchronise; two models: no-ops.
 int mcmc_tables1_hold(mceik_mcmc *s, const char *who);
 int mcmc_tables1_drop(mceik_mcmc *s);
+// The lifecycle of a kept-state accumulator k of s (sampler_api.hip), behind
+// the four files' entry points.  kept_enable_held is enable's tail once the
+// options are valid, `same` saying that the held state has them.  It returns
+// what enable returns when the call is decided (the held sums go on: 0 or
+// mcmc_tables1_hold's code; held states of other options are refused: 1; a
+// HIP failure: -1), or KEPT_REPLACE once the old state is gone (synchronised,
+// freed): the caller builds its state, allocates its arrays and ends with
+// kept_publish, or frees a failed one with kept_state_free.
+#define KEPT_REPLACE (-2)
+int kept_enable_held(mceik_mcmc *s, KeptStream &k, bool same, const char *who);
+int kept_publish(mceik_mcmc *s, KeptStream &k, void *state, const char *who);
+void kept_state_free(KeptStream &k, void *state);
+int kept_disable(mceik_mcmc *s, KeptStream &k);                 // stop adding; the sums stay
+int kept_clear(mceik_mcmc *s, KeptStream &k);                   // drop the state (synchronises)
+int kept_accumulate(mceik_mcmc *s, KeptStream &k);              // the cold chains' current state, now
+int kept_get(mceik_mcmc *s, KeptStream &k, long long *n, void *const *host);
+int kept_set(mceik_mcmc *s, KeptStream &k, long long n, const void *const *host);
 // Bytes pipe k's Langevin step needs for chunks of m chains: the fields (u), the
 // workspaces of the forward with fields (fws) and of the adjoint (aws), the
 // pick weights (evw) and the adjoint's per-solve rows (gs), each a multiple of

@@ -499,6 +499,10 @@ extern "C" int mceik_mcmc_init(const struct mceik_parms_struct *parms, const str
     DeviceScope dg(o->device);
     if (hipSetDevice(o->device) != hipSuccess) return -1;
     mceik_mcmc *s = new mceik_mcmc();
+    s->kept[KEPT_POST] = mcmc_post_stream();
+    s->kept[KEPT_COV] = mcmc_cov_stream();
+    s->kept[KEPT_ESS] = mcmc_ess_stream();
+    s->kept[KEPT_FIT] = mcmc_fit_stream();
     s->device = o->device;
     s->stream = nullptr;
     s->step = 0;
@@ -812,35 +816,39 @@ static StepPlan plan_step(const mceik_mcmc *s, long long gs)
 }
 
 // The kept-state hook.  Seven consumers see the cold chains of a kept step:
-// posterior, hypocentre moments, nuisance moments, covariances, batch means,
-// data fit, Voronoi moments.
+// the four accumulators of s->kept (posterior, covariances, batch means, data
+// fit) and the moments that live in their moves' state (hypocentre, nuisance,
+// Voronoi).
 // kept_queue queues those that are on for the cold chains of pipe p's view on
 // stream st; kept_counted counts the state on the host once every pipe is
-// queued (mcmc_ess_k depends on that count alone, so every pipe reads the
-// same k).  One pipe views every chain, so the multi-step branch calls the
+// queued (an accumulator is handed the count before the step, so every pipe
+// passes the same one).  One pipe views every chain, so the multi-step branch calls the
 // same two, where mcmc_multi_step rules the hypocentre and nuisance moments out.
 static int kept_queue(mceik_mcmc *s, const Pipe &p, hipStream_t st)
 {
     const int off = p.D.chain_offset - s->D.chain_offset, n = cold_in(s, off, p.D.nchains);
     if (n <= 0) return 0;
-    if (s->post) HIPCHK(mcmc_post_accumulate(s->post, p.D, off, n, st));
+    for (const KeptStream &k : s->kept)
+        if (k.on) HIPCHK(k.accumulate(k.state, p.D, p.H, p.N, off, n, k.n, st));
     if (s->hypo_on) HIPCHK(hypo_moments(p.D, p.H, n, st));
     if (s->nuis_on && s->N.kn) HIPCHK(nuis_moments(p.D, p.N, n, st));
-    if (s->cov_on) HIPCHK(mcmc_cov_accumulate(s->cov, p.D, p.H, p.N, off, n, st));
-    if (s->ess_on) HIPCHK(mcmc_ess_accumulate(s->ess, p.D, p.H, p.N, off, n, mcmc_ess_k(s->ess), st));
-    if (s->fit_on) HIPCHK(mcmc_fit_accumulate(s->fit, p.D, p.H, p.N, off, n, st));
     if (s->vor_on) HIPCHK(vor_moments(p.D, p.V, n, st));
     return 0;
 }
 
+static bool kept_any_on(const mceik_mcmc *s)
+{
+    for (const KeptStream &k : s->kept)
+        if (k.on) return true;
+    return false;
+}
+
 static void kept_counted(mceik_mcmc *s)
 {
-    if (s->post) mcmc_post_counted(s->post);
+    for (KeptStream &k : s->kept)
+        if (k.on) k.n++;
     if (s->hypo_on) s->hyp_n += temper_cold(s);
     if (s->nuis_on && s->N.kn) s->nuis_n += temper_cold(s);
-    if (s->cov_on) mcmc_cov_counted(s->cov);
-    if (s->ess_on) mcmc_ess_counted(s->ess);
-    if (s->fit_on) mcmc_fit_counted(s->fit);
     if (s->vor_on) s->vor_n += temper_cold(s);
 }
 
@@ -1015,9 +1023,9 @@ static int mcmc_steps(mceik_mcmc *s, int nsteps)
         // FSM launch (the kernel accepts, keeps and proposes the rest)
         for (int done = 0; done < nsteps;) {
             int n = std::min(nsteps - done, MCEIK_MC_CHUNK);
-            // posterior, covariances, batch means or data fit on: the launch ends right after the
+            // an accumulator of kept states on: the launch ends right after the
             // next kept step, when every chain's current state is its state after that step
-            if (s->post || s->cov_on || s->ess_on || s->fit_on) n = (int)std::min<long long>(n, next_kept_step(s) - s->step + 1);
+            if (kept_any_on(s)) n = (int)std::min<long long>(n, next_kept_step(s) - s->step + 1);
             // tempering: this step's swap round first; the launch ends before the next one
             const StepPlan q = plan_step(s, s->step);         // (a velocity step: mcmc_multi_step)
             if (q.swap && temper_round(s, q.parity)) return -1;
@@ -1149,10 +1157,7 @@ extern "C" int mceik_mcmc_finalize(mceik_mcmc **ps)
     for (Pipe &p : s->pipe) if (p.ws_own && p.ws) hipFree(p.ws);
     for (LangPipe &lp : s->lang_pipe) if (lp.base) hipFree(lp.base);
     for (void *p : s->allocs) hipFree(p);
-    mcmc_post_free(s->post);
-    mcmc_cov_free(s->cov);
-    mcmc_ess_free(s->ess);
-    mcmc_fit_free(s->fit);
+    for (KeptStream &k : s->kept) kept_state_free(k, k.state);
     for (int i = 0; i < 2 * s->ev_made; i++) hipEventDestroy(s->ev[i]);
     if (s->ws) hipFree(s->ws);
     delete s;

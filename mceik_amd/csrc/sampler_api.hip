@@ -31,7 +31,7 @@ static int vor_refuses(const mceik_mcmc *s, const char *who)
 }
 
 // The posterior holds states: a change of what the chains sample is refused.
-static bool post_holds_states(const mceik_mcmc *s) { return s->post && mcmc_post_count(s->post) > 0; }
+static bool post_holds_states(const mceik_mcmc *s) { return s->kept[KEPT_POST].state && s->kept[KEPT_POST].n > 0; }
 
 // The body of the *_stats entry points: n words of each counter array to the
 // host (synchronises), then with reset nreset zero words from `zero` on.
@@ -74,12 +74,102 @@ int mcmc_tables1_hold(mceik_mcmc *s, const char *who)
 
 int mcmc_tables1_drop(mceik_mcmc *s)
 {
-    if (s->D.nphase != 1 || !s->D.ttab_cur || s->N.kn || s->fit_on) return 0;
+    if (s->D.nphase != 1 || !s->D.ttab_cur || s->N.kn || kept_needs_tables1(s)) return 0;
     DeviceScope dg(s->device);
     HIPCHK(hipStreamSynchronize(s->stream));
     s->D.ttab_cur = nullptr;
     s->fb_all.ttab = s->fb.ttab;
     return pipes_refresh(s);
+}
+
+// ---------------------------------------------------------------------------
+// the lifecycle of the accumulators of kept states (sampler.h; kept.h)
+
+void kept_state_free(KeptStream &k, void *state)
+{
+    if (!state) return;
+    KeptArray a[KEPT_MAX_ARRAYS];
+    kept_arrays_free(a, k.arrays(state, a));
+    k.free_extra(state);
+}
+
+int kept_enable_held(mceik_mcmc *s, KeptStream &k, bool same, const char *who)
+{
+    if (k.state && same) {                           // the held sums go on
+        k.on = true;
+        return k.needs_tables1 ? mcmc_tables1_hold(s, who) : 0;
+    }
+    if (k.state && k.n > 0) return 1;                // held states of other options
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    void *old = k.state;
+    k.state = nullptr;
+    k.on = false;
+    k.n = 0;
+    kept_state_free(k, old);
+    return KEPT_REPLACE;
+}
+
+int kept_publish(mceik_mcmc *s, KeptStream &k, void *state, const char *who)
+{
+    k.state = state;
+    k.on = true;
+    k.n = 0;
+    return k.needs_tables1 ? mcmc_tables1_hold(s, who) : 0;
+}
+
+int kept_disable(mceik_mcmc *s, KeptStream &k)
+{
+    if (!k.on) return 0;
+    k.on = false;                      // host state only: queued steps keep the kernels they were queued with
+    return k.needs_tables1 ? mcmc_tables1_drop(s) : 0;   // (a one-model sampler stops holding its current tables unless nuisance state needs them)
+}
+
+int kept_clear(mceik_mcmc *s, KeptStream &k)
+{
+    if (!k.state) return 0;
+    DeviceScope dg(s->device);
+    const hipError_t e = hipStreamSynchronize(s->stream);
+    kept_state_free(k, k.state);
+    k.state = nullptr;
+    k.on = false;
+    k.n = 0;
+    const int rc = k.needs_tables1 ? mcmc_tables1_drop(s) : 0;
+    return e == hipSuccess ? rc : -1;
+}
+
+int kept_accumulate(mceik_mcmc *s, KeptStream &k)
+{
+    if (!k.state || !k.on) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(k.accumulate(k.state, s->D, s->H, s->N, 0, temper_cold(s), k.n, s->stream));   // tempering: the cold chains
+    k.n++;
+    return 0;
+}
+
+int kept_get(mceik_mcmc *s, KeptStream &k, long long *n, void *const *host)
+{
+    if (!k.state) return 1;
+    if (mceik_mcmc_sync(s)) return -1;
+    DeviceScope dg(s->device);
+    if (n) *n = k.n;
+    KeptArray a[KEPT_MAX_ARRAYS];
+    const int na = k.arrays(k.state, a);
+    HIPCHK(kept_arrays_copy(a, na, host, true));
+    return 0;
+}
+
+int kept_set(mceik_mcmc *s, KeptStream &k, long long n, const void *const *host)
+{
+    if (!k.state || n < 0) return 1;
+    KeptArray a[KEPT_MAX_ARRAYS];
+    const int na = k.arrays(k.state, a);
+    if (kept_arrays_missing(a, na, host)) return 1;
+    DeviceScope dg(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    HIPCHK(kept_arrays_copy(a, na, (void *const *)host, false));
+    k.n = n;
+    return 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -89,10 +179,8 @@ int mcmc_tables1_drop(mceik_mcmc *s)
 // chains sample would mix two posteriors in its sums.
 static const char *kept_stream_holding(const mceik_mcmc *s)
 {
-    if (post_holds_states(s)) return "the streaming posterior";
-    if (s->cov && s->cov_on && mcmc_cov_count(s->cov) > 0) return "the covariance sums";
-    if (s->ess && s->ess_on && mcmc_ess_count(s->ess) > 0) return "the batch-means sums";
-    if (s->fit && s->fit_on && mcmc_fit_count(s->fit) > 0) return "the data-fit sums";
+    for (const KeptStream &k : s->kept)
+        if (k.on && k.n > 0) return k.name;
     if (s->hypo_on && s->hyp_n > 0) return "the hypocentre moments";
     if (s->nuis_on && s->nuis_n > 0) return "the noise / statics moments";
     if (s->vor_on && s->vor_n > 0) return "the Voronoi-cell moments";
@@ -768,13 +856,13 @@ extern "C" int mceik_mcmc_nuis_clear(mceik_mcmc *s)
     if (!s) return 1;
     if (!s->N.kn) return 0;
     if (post_holds_states(s)) return 1;
-    if (s->cov_on && mcmc_cov_holds_nuis(s->cov)) return 1;   // a registered probe reads the values
-    if (s->ess_on && mcmc_ess_holds_nuis(s->ess)) return 1;   // likewise
+    for (const KeptStream &k : s->kept)
+        if (k.on && k.holds_nuis && k.holds_nuis(k.state)) return 1;   // a registered probe reads the values
     DeviceScope dg(s->device);
     HIPCHK(hipStreamSynchronize(s->stream));
     s->nuis_on = false;
     memset(&s->N, 0, sizeof(s->N));
-    if (s->D.nphase == 1 && !s->fit_on) {       // (the data-fit sums keep reading the current tables)
+    if (s->D.nphase == 1 && !kept_needs_tables1(s)) {       // (the data-fit sums keep reading the current tables)
         s->D.ttab_cur = nullptr;
         s->fb_all.ttab = s->fb.ttab;
     }

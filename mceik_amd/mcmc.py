@@ -602,6 +602,86 @@ def _nuis_same(a, b):
 _DE_COUNTERS = ("attempts", "accepts", "outbox", "failed", "moved")
 
 
+class _Kept:
+    """One accumulator of kept states as `Sampler` drives it (csrc/kept.h has the
+    C side): `stem` of its mceik_mcmc_<stem>_* entry points and its checkpoint
+    key, the Sampler attribute `attr` that holds the enabled options, and as
+    functions of the sampler and those options the ordered table of its arrays
+    `{key: (shape, dtype)}` (the order of get / set; `slots`: the full argument
+    list where an option leaves arrays out), the `extra` entries of `*_raw()`,
+    whether a checkpoint entry was taken with the `same` options, and the
+    empty `*Partials`."""
+
+    def __init__(self, stem, attr, not_enabled, mismatch, arrays, extra, same, partials, slots=None):
+        self.stem, self.attr, self.not_enabled, self.mismatch = stem, attr, not_enabled, mismatch
+        self.arrays, self.extra, self.same, self.partials, self.slots = arrays, extra, same, partials, slots
+
+
+def _probe_list(raw):
+    return [tuple(int(x) for x in pr) for pr in raw["probes"]]
+
+
+def _posterior_arrays(smp, held):
+    per_chain, nbins = held
+    shape = smp.model_shape if per_chain else smp.model_shape[1:]
+    return {"sum": (shape, np.int64), "sumsq": (shape, np.int64), "hist": (smp.model_shape[1:] + (nbins,), np.uint32)}
+
+
+def _cov_arrays(smp, held):
+    lst, within = held
+    n, ncm, nch = len(lst), smp.p.nphase * smp.p.ncell, smp.nchains
+    shapes = {"A": (n,), "G": (n, n), "S": (ncm,), "Q": (ncm,), "C": (n, ncm)}
+    if within:
+        shapes.update({"Ac": (nch, n), "Sc": (nch, ncm)})
+    return {k: (sh, np.int64) for k, sh in shapes.items()}
+
+
+def _ess_arrays(smp, held):
+    L, lst = held
+    ne, nch = smp.p.nphase * smp.p.ncell + len(lst), smp.nchains
+    return {"Sc": ((nch, ne), np.int64), "pend": ((L - 1, nch, ne), np.int32), "A": ((L, ne), np.int64),
+            "Q": ((L, ne, 2), np.uint64), "P": ((L, ne, 2), np.uint64)}
+
+
+def _fit_arrays(smp, held):
+    nbins, p = held[1], smp.p
+    nobs, nev = len(p.tobs), p.nevents
+    return {"sq": ((nobs,), np.int64), "szq": ((nobs,), np.int64), "sq2": ((nobs, 2), np.uint64),
+            "szq2": ((nobs, 2), np.uint64), "stq": ((nev,), np.int64), "stq2": ((nev, 2), np.uint64),
+            "hist": ((max(1, p.nphase), p.nstat, nbins), np.int64), "sat": ((3,), np.int64)}
+
+
+def _posterior_parts(smp, held):
+    p = smp.p
+    bounds = [(p.vmin, p.vmax), (p.vsmin, p.vsmax)][:p.nphase]
+    return PosteriorPartials(p.nphase * p.ncell, held[1], held[0], shape=smp.model_shape[1:], bounds=bounds)
+
+
+_KEPT = {d.stem: d for d in (
+    _Kept("posterior", "_post", "the posterior is not enabled (Sampler.posterior_enable)",
+          "the checkpoint's posterior was accumulated with other options", _posterior_arrays,
+          lambda held: {"per_chain": held[0], "nbins": held[1]},
+          lambda held, raw: (bool(raw["per_chain"]), int(raw["nbins"])) == held, _posterior_parts),
+    _Kept("cov", "_cov", "the covariances are not enabled (Sampler.cov_enable)",
+          "the checkpoint's covariance sums were accumulated with another probe list or `within`", _cov_arrays,
+          lambda held: {"probes": list(held[0]), "within": held[1]},
+          lambda held, raw: (_probe_list(raw), bool(raw["within"])) == held,
+          lambda smp, held: CovPartials(held[0], smp.p.nphase * smp.p.ncell, held[1], shape=smp.model_shape[1:]),
+          slots=("A", "G", "S", "Q", "C", "Ac", "Sc")),
+    _Kept("ess", "_ess", "the batch-means sums are not enabled (Sampler.ess_enable)",
+          "the checkpoint's batch-means sums were accumulated with another nlevels or probe list", _ess_arrays,
+          lambda held: {"nlevels": held[0], "probes": list(held[1])},
+          lambda held, raw: (int(raw["nlevels"]), _probe_list(raw)) == held,
+          lambda smp, held: EssPartials(smp.p.nphase * smp.p.ncell, held[0], probes=held[1], shape=smp.model_shape[1:])),
+    _Kept("fit", "_fit", "the data-fit sums are not enabled (Sampler.fit_enable)",
+          "the checkpoint's data-fit sums were accumulated with other options", _fit_arrays,
+          lambda held: {"tick": held[0], "nbins": held[1], "zmax": held[2], "t0_ref": held[3].copy()},
+          lambda held, raw: (float(raw["tick"]), int(raw["nbins"]), float(raw["zmax"])) == held[:3] and
+          np.asarray(raw["t0_ref"], np.float64).tobytes() == held[3].tobytes(),
+          lambda smp, held: FitPartials(len(smp.p.tobs), smp.p.nevents, max(1, smp.p.nphase), smp.p.nstat, held[1],
+                                        held[0], held[2])))}
+
+
 class Sampler:
     """One GPU's chains (include/mceik.h handle)."""
 
@@ -761,8 +841,9 @@ class Sampler:
         ck = {"v": v, "logl": logl, "naccept": nacc, "step": step.value, "nkept": nkept.value,
               "chain_offset": self.chain_offset, "seed": self.p.seed,
               "likelihood": self.likelihood}      # the norm decides what logl means
-        if self._post is not None:       # the accumulators belong to the state of a run that summarises itself
-            ck["posterior"] = self.posterior_raw()
+        for d in _KEPT.values():         # the accumulators, open batches included, belong to the state of a run that
+            if getattr(self, d.attr) is not None:                                               # summarises itself
+                ck[d.stem] = self._kept_raw(d)
         if self._temper is not None:     # the ladder decides what the chains sample; the counters ride along
             att, acc = self.temper_stats()
             ck["temper"] = {"betas": self._temper[0].copy(), "swap_every": self._temper[1],
@@ -788,12 +869,6 @@ class Sampler:
             kn, kc = self.nuis_get()
             ck["nuis"] = {"opts": dict(self._nuis), "kn": kn, "kc": kc, "attempts": att, "accepts": acc,
                           "moments": self.nuis_moments()}
-        if self._cov is not None:        # the sums belong to the state of a run that summarises itself
-            ck["cov"] = self.cov_raw()
-        if self._ess is not None:        # likewise: the open batches are part of a run that summarises itself
-            ck["ess"] = self.ess_raw()
-        if self._fit is not None:        # likewise
-            ck["fit"] = self.fit_raw()
         return ck
 
     def restore(self, ck, recompute_logl=False):
@@ -843,19 +918,11 @@ class Sampler:
             recompute_logl = True
         if self._fit_active and self.p.nphase == 1:
             recompute_logl = True        # a one-model sampler holds current tables for the data-fit sums: the forward makes them
-        ck_cov = ck.get("cov")           # a sampler without the sums ignores the entry; one with them wants its list
-        if ck_cov is not None and self._cov is not None and \
-                ([tuple(int(x) for x in pr) for pr in ck_cov["probes"]], bool(ck_cov["within"])) != self._cov:
-            raise ValueError("the checkpoint's covariance sums were accumulated with another probe list or `within`")
-        ck_ess = ck.get("ess")           # likewise; the open batches of another hierarchy mean nothing here
-        if ck_ess is not None and self._ess is not None and \
-                (int(ck_ess["nlevels"]), [tuple(int(x) for x in pr) for pr in ck_ess["probes"]]) != self._ess:
-            raise ValueError("the checkpoint's batch-means sums were accumulated with another nlevels or probe list")
-        ck_fit = ck.get("fit")           # likewise
-        if ck_fit is not None and self._fit is not None and \
-                ((float(ck_fit["tick"]), int(ck_fit["nbins"]), float(ck_fit["zmax"])) != self._fit[:3] or
-                 np.asarray(ck_fit["t0_ref"], np.float64).tobytes() != self._fit[3].tobytes()):
-            raise ValueError("the checkpoint's data-fit sums were accumulated with other options")
+        # a sampler without an accumulator ignores the checkpoint's entry; one with it wants sums of its own options
+        kept = [(d, ck[d.stem]) for d in _KEPT.values() if ck.get(d.stem) is not None and getattr(self, d.attr) is not None]
+        for d, raw in kept:
+            if not d.same(getattr(self, d.attr), raw):
+                raise ValueError(d.mismatch)
         v = np.ascontiguousarray(ck["v"], dtype=np.int32)
         assert v.shape == self.model_shape
         logl = None if recompute_logl else np.ascontiguousarray(ck["logl"], dtype=np.float64)
@@ -867,8 +934,8 @@ class Sampler:
             raise RuntimeError(f"mceik_mcmc_restore failed ({rc})")
         if recompute_logl:
             self._last_full = True
-        if "posterior" in ck and self._post is not None:
-            self._posterior_set(ck["posterior"])
+        for d, raw in kept:
+            self._kept_set(d, raw)
         if tk is not None:
             self._rebase_stats("temper", tk)
         if bk is not None:
@@ -892,12 +959,6 @@ class Sampler:
         if nk is not None:
             self._rebase_stats("nuis", nk)
             self.nuis_moments_set(nk["moments"])
-        if ck_cov is not None and self._cov is not None:
-            self._cov_set(ck_cov)
-        if ck_ess is not None and self._ess is not None:
-            self._ess_set(ck_ess)
-        if ck_fit is not None and self._fit is not None:
-            self._fit_set(ck_fit)
 
     # --- attempt / accept counters of the moves (mceik_mcmc_{temper,block,hypo,nuis}_stats) ---
     def _move_stats(self, name, n, reset, why=""):
@@ -933,63 +994,85 @@ class Sampler:
         self._post = (bool(per_chain), int(nbins))
 
     def posterior_disable(self):
-        if self._L.mceik_mcmc_posterior_disable(self._h) != 0:
-            raise RuntimeError("mceik_mcmc_posterior_disable failed")
-        self._post = None
-
-    def _posterior_on(self):
-        if self._post is None:
-            raise RuntimeError("the posterior is not enabled (Sampler.posterior_enable)")
-        return self._post
+        self._kept_clear(_KEPT["posterior"], "disable")
 
     def posterior_accumulate(self):
         """Add the chains' current state to the accumulators now (enqueued)."""
-        self._posterior_on()
-        rc = self._L.mceik_mcmc_posterior_accumulate(self._h)
-        if rc != 0:
-            raise RuntimeError(f"mceik_mcmc_posterior_accumulate failed ({rc})")
+        self._kept_accumulate(_KEPT["posterior"])
 
     def posterior_raw(self):
         """The accumulators as host arrays: {"n": states per chain, "sum", "sumsq":
         int64 shaped like model_shape (per chain) or model_shape[1:] (pooled),
         "hist": uint32 model_shape[1:] + (nbins,), "per_chain", "nbins"}."""
-        per_chain, nbins = self._posterior_on()
-        shape = self.model_shape if per_chain else self.model_shape[1:]
-        sm, sq = np.empty(shape, np.int64), np.empty(shape, np.int64)
-        hist = np.empty(self.model_shape[1:] + (nbins,), np.uint32)
-        n = C.c_longlong(0)
-        rc = self._L.mceik_mcmc_posterior_get(self._h, C.byref(n), sm.ctypes.data_as(C.c_void_p),
-                                              sq.ctypes.data_as(C.c_void_p), hist.ctypes.data_as(C.c_void_p))
-        if rc != 0:
-            raise RuntimeError(f"mceik_mcmc_posterior_get failed ({rc})")
-        return {"n": n.value, "sum": sm, "sumsq": sq, "hist": hist, "per_chain": per_chain, "nbins": nbins}
+        return self._kept_raw(_KEPT["posterior"])
 
     def _posterior_set(self, raw):
-        per_chain, nbins = self._posterior_on()
-        if bool(raw["per_chain"]) != per_chain or int(raw["nbins"]) != nbins:
-            raise ValueError("the checkpoint's posterior was accumulated with other options")
-        shape = self.model_shape if per_chain else self.model_shape[1:]
-        sm = np.ascontiguousarray(raw["sum"], dtype=np.int64)
-        sq = np.ascontiguousarray(raw["sumsq"], dtype=np.int64)
-        hist = np.ascontiguousarray(raw["hist"], dtype=np.uint32)
-        assert sm.shape == shape and sq.shape == shape and hist.shape == self.model_shape[1:] + (nbins,)
-        rc = self._L.mceik_mcmc_posterior_set(self._h, int(raw["n"]), sm.ctypes.data_as(C.c_void_p),
-                                              sq.ctypes.data_as(C.c_void_p), hist.ctypes.data_as(C.c_void_p))
-        if rc != 0:
-            raise RuntimeError(f"mceik_mcmc_posterior_set failed ({rc})")
+        d = _KEPT["posterior"]
+        if not d.same(self._kept_on(d), raw):
+            raise ValueError(d.mismatch)
+        self._kept_set(d, raw)
 
     def posterior_partials(self):
         """The chain axis summed on the GPU into exact partials
         (`PosteriorPartials`): what ranks exchange and merge."""
-        per_chain, nbins = self._posterior_on()
-        p = self.p
-        bounds = [(p.vmin, p.vmax), (p.vsmin, p.vsmax)][:p.nphase]
-        out = PosteriorPartials(p.nphase * p.ncell, nbins, per_chain, shape=self.model_shape[1:], bounds=bounds)
-        st = out._struct()
-        rc = self._L.mceik_mcmc_posterior_partials(self._h, C.byref(st))
+        return self._kept_partials(_KEPT["posterior"])
+
+    # --- the accumulators of kept states: one implementation over the rows of _KEPT ---
+    def _kept_on(self, d):
+        """The enabled options of accumulator `d`; RuntimeError while it is not enabled."""
+        held = getattr(self, d.attr)
+        if held is None:
+            raise RuntimeError(d.not_enabled)
+        return held
+
+    def _kept_call(self, d, what, *args):
+        return getattr(self._L, f"mceik_mcmc_{d.stem}_{what}")(self._h, *args)
+
+    def _kept_disable(self, d):
+        if self._kept_call(d, "disable") != 0:
+            raise RuntimeError(f"mceik_mcmc_{d.stem}_disable failed")
+
+    def _kept_clear(self, d, what="clear"):
+        if self._kept_call(d, what) != 0:
+            raise RuntimeError(f"mceik_mcmc_{d.stem}_{what} failed")
+        setattr(self, d.attr, None)
+
+    def _kept_accumulate(self, d):
+        self._kept_on(d)
+        rc = self._kept_call(d, "accumulate")
         if rc != 0:
-            raise RuntimeError(f"mceik_mcmc_posterior_partials failed ({rc})")
-        out.nchains, out.nkept = int(st.nchains), int(st.nkept)
+            raise RuntimeError(f"mceik_mcmc_{d.stem}_accumulate failed ({rc})")
+
+    @staticmethod
+    def _kept_ptrs(d, arr):
+        return [arr[k].ctypes.data_as(C.c_void_p) if k in arr else None for k in (d.slots or arr)]
+
+    def _kept_raw(self, d):
+        held = self._kept_on(d)
+        out = {k: np.zeros(sh, dt) for k, (sh, dt) in d.arrays(self, held).items()}
+        n = C.c_longlong(0)
+        rc = self._kept_call(d, "get", C.byref(n), *self._kept_ptrs(d, out))
+        if rc != 0:
+            raise RuntimeError(f"mceik_mcmc_{d.stem}_get failed ({rc})")
+        out["n"] = n.value
+        out.update(d.extra(held))
+        return out
+
+    def _kept_set(self, d, raw):
+        table = d.arrays(self, self._kept_on(d))
+        arr = {k: np.ascontiguousarray(raw[k], dtype=dt) for k, (sh, dt) in table.items()}
+        assert all(arr[k].shape == sh for k, (sh, dt) in table.items())
+        rc = self._kept_call(d, "set", int(raw["n"]), *self._kept_ptrs(d, arr))
+        if rc != 0:
+            raise RuntimeError(f"mceik_mcmc_{d.stem}_set failed ({rc})")
+
+    def _kept_partials(self, d):
+        out = d.partials(self, self._kept_on(d))
+        st = out._struct()
+        rc = self._kept_call(d, "partials", C.byref(st))
+        if rc != 0:
+            raise RuntimeError(f"mceik_mcmc_{d.stem}_partials failed ({rc})")
+        out._took(st)
         return out
 
     # --- parallel tempering (include/mceik.h mceik_mcmc_temper_*) ---
@@ -1767,68 +1850,29 @@ class Sampler:
 
     def cov_disable(self):
         """Stop accumulating; the sums stay (`cov_raw`, `cov_partials`, a later `cov_enable` of the same list)."""
-        if self._L.mceik_mcmc_cov_disable(self._h) != 0:
-            raise RuntimeError("mceik_mcmc_cov_disable failed")
+        self._kept_disable(_KEPT["cov"])
 
     def cov_clear(self):
         """Drop the sums and the probe list."""
-        if self._L.mceik_mcmc_cov_clear(self._h) != 0:
-            raise RuntimeError("mceik_mcmc_cov_clear failed")
-        self._cov = None
-
-    def _cov_on(self):
-        if self._cov is None:
-            raise RuntimeError("the covariances are not enabled (Sampler.cov_enable)")
-        return self._cov
+        self._kept_clear(_KEPT["cov"])
 
     def cov_accumulate(self):
         """Add the cold chains' current state to the sums now (enqueued)."""
-        self._cov_on()
-        rc = self._L.mceik_mcmc_cov_accumulate(self._h)
-        if rc != 0:
-            raise RuntimeError(f"mceik_mcmc_cov_accumulate failed ({rc})")
-
-    def _cov_arrays(self):
-        lst, within = self._cov_on()
-        n, ncm, nch = len(lst), self.p.nphase * self.p.ncell, self.nchains
-        shapes = {"A": (n,), "G": (n, n), "S": (ncm,), "Q": (ncm,), "C": (n, ncm)}
-        if within:
-            shapes.update({"Ac": (nch, n), "Sc": (nch, ncm)})
-        return shapes
+        self._kept_accumulate(_KEPT["cov"])
 
     def cov_raw(self):
         """The accumulators as host arrays: {"n": states per chain, "probes":
         [(kind, index)], "within", int64 "A" [np], "G" [np, np], "S", "Q" [ncm],
         "C" [np, ncm] and with `within` "Ac" [nchains, np], "Sc" [nchains, ncm]}."""
-        lst, within = self._cov_on()
-        out = {k: np.empty(sh, np.int64) for k, sh in self._cov_arrays().items()}
-        n = C.c_longlong(0)
-        ptr = [out[k].ctypes.data_as(C.c_void_p) if k in out else None for k in ("A", "G", "S", "Q", "C", "Ac", "Sc")]
-        rc = self._L.mceik_mcmc_cov_get(self._h, C.byref(n), *ptr)
-        if rc != 0:
-            raise RuntimeError(f"mceik_mcmc_cov_get failed ({rc})")
-        out.update({"n": n.value, "probes": list(lst), "within": within})
-        return out
+        return self._kept_raw(_KEPT["cov"])
 
     def _cov_set(self, raw):
-        arr = {k: np.ascontiguousarray(raw[k], dtype=np.int64) for k in self._cov_arrays()}
-        assert all(arr[k].shape == sh for k, sh in self._cov_arrays().items())
-        ptr = [arr[k].ctypes.data_as(C.c_void_p) if k in arr else None for k in ("A", "G", "S", "Q", "C", "Ac", "Sc")]
-        rc = self._L.mceik_mcmc_cov_set(self._h, int(raw["n"]), *ptr)
-        if rc != 0:
-            raise RuntimeError(f"mceik_mcmc_cov_set failed ({rc})")
+        self._kept_set(_KEPT["cov"], raw)
 
     def cov_partials(self):
         """The sums as exact partials (`CovPartials`), the chain axis of the
         per-chain sums reduced on the GPU: what ranks exchange and merge."""
-        lst, within = self._cov_on()
-        out = CovPartials(lst, self.p.nphase * self.p.ncell, within, shape=self.model_shape[1:])
-        st = out._struct()
-        rc = self._L.mceik_mcmc_cov_partials(self._h, C.byref(st))
-        if rc != 0:
-            raise RuntimeError(f"mceik_mcmc_cov_partials failed ({rc})")
-        out.nchains, out.nkept = int(st.nchains), int(st.nkept)
-        return out
+        return self._kept_partials(_KEPT["cov"])
 
     # --- effective sample sizes by batch means (include/mceik.h mceik_mcmc_ess_*) ---
     def ess_enable(self, nlevels=8, probes=()):
@@ -1860,64 +1904,29 @@ class Sampler:
 
     def ess_disable(self):
         """Stop accumulating; the sums stay (`ess_raw`, `ess_partials`, a later `ess_enable` of the same options)."""
-        if self._L.mceik_mcmc_ess_disable(self._h) != 0:
-            raise RuntimeError("mceik_mcmc_ess_disable failed")
+        self._kept_disable(_KEPT["ess"])
 
     def ess_clear(self):
         """Drop the sums."""
-        if self._L.mceik_mcmc_ess_clear(self._h) != 0:
-            raise RuntimeError("mceik_mcmc_ess_clear failed")
-        self._ess = None
-
-    def _ess_on(self):
-        if self._ess is None:
-            raise RuntimeError("the batch-means sums are not enabled (Sampler.ess_enable)")
-        return self._ess
+        self._kept_clear(_KEPT["ess"])
 
     def ess_accumulate(self):
         """Add the cold chains' current state to the sums now (enqueued)."""
-        self._ess_on()
-        rc = self._L.mceik_mcmc_ess_accumulate(self._h)
-        if rc != 0:
-            raise RuntimeError(f"mceik_mcmc_ess_accumulate failed ({rc})")
-
-    def _ess_arrays(self):
-        L, lst = self._ess_on()
-        ne, nch = self.p.nphase * self.p.ncell + len(lst), self.nchains
-        return {"Sc": ((nch, ne), np.int64), "pend": ((L - 1, nch, ne), np.int32), "A": ((L, ne), np.int64),
-                "Q": ((L, ne, 2), np.uint64), "P": ((L, ne, 2), np.uint64)}
+        self._kept_accumulate(_KEPT["ess"])
 
     def ess_raw(self):
         """The accumulators as host arrays: {"n": states per chain, "nlevels",
         "probes": [(kind, index)], "Sc" int64 [nchains, ne], "pend" int32
         [nlevels - 1, nchains, ne], "A" int64 [nlevels, ne], "Q", "P" uint64
         [nlevels, ne, 2] (lo, hi words)}; ne = the model entries, then the probes."""
-        L, lst = self._ess_on()
-        out = {k: np.zeros(sh, dt) for k, (sh, dt) in self._ess_arrays().items()}
-        n = C.c_longlong(0)
-        rc = self._L.mceik_mcmc_ess_get(self._h, C.byref(n), *(out[k].ctypes.data_as(C.c_void_p) for k in out))
-        if rc != 0:
-            raise RuntimeError(f"mceik_mcmc_ess_get failed ({rc})")
-        out.update({"n": n.value, "nlevels": L, "probes": list(lst)})
-        return out
+        return self._kept_raw(_KEPT["ess"])
 
     def _ess_set(self, raw):
-        arr = {k: np.ascontiguousarray(raw[k], dtype=dt) for k, (sh, dt) in self._ess_arrays().items()}
-        assert all(arr[k].shape == sh for k, (sh, dt) in self._ess_arrays().items())
-        rc = self._L.mceik_mcmc_ess_set(self._h, int(raw["n"]), *(arr[k].ctypes.data_as(C.c_void_p) for k in arr))
-        if rc != 0:
-            raise RuntimeError(f"mceik_mcmc_ess_set failed ({rc})")
+        self._kept_set(_KEPT["ess"], raw)
 
     def ess_partials(self):
         """The pooled sums as exact partials (`EssPartials`): what ranks exchange and merge."""
-        L, lst = self._ess_on()
-        out = EssPartials(self.p.nphase * self.p.ncell, L, probes=lst, shape=self.model_shape[1:])
-        st = out._struct()
-        rc = self._L.mceik_mcmc_ess_partials(self._h, C.byref(st))
-        if rc != 0:
-            raise RuntimeError(f"mceik_mcmc_ess_partials failed ({rc})")
-        out.nchains, out.nkept = int(st.nchains), int(st.nkept)
-        return out
+        return self._kept_partials(_KEPT["ess"])
 
     # --- pick residuals, origin times and data-fit checks (include/mceik.h mceik_mcmc_fit_*) ---
     def fit_enable(self, tick=2.0 ** -20, nbins=64, zmax=8.0, t0_ref=None):
@@ -1953,36 +1962,17 @@ class Sampler:
 
     def fit_disable(self):
         """Stop accumulating; the sums stay (`fit_raw`, `fit_partials`, a later `fit_enable` of the same options)."""
-        if self._L.mceik_mcmc_fit_disable(self._h) != 0:
-            raise RuntimeError("mceik_mcmc_fit_disable failed")
+        self._kept_disable(_KEPT["fit"])
         self._fit_active = False
 
     def fit_clear(self):
         """Drop the sums."""
-        if self._L.mceik_mcmc_fit_clear(self._h) != 0:
-            raise RuntimeError("mceik_mcmc_fit_clear failed")
-        self._fit = None
+        self._kept_clear(_KEPT["fit"])
         self._fit_active = False
-
-    def _fit_on(self):
-        if self._fit is None:
-            raise RuntimeError("the data-fit sums are not enabled (Sampler.fit_enable)")
-        return self._fit
 
     def fit_accumulate(self):
         """Add the cold chains' current state to the sums now (enqueued)."""
-        self._fit_on()
-        rc = self._L.mceik_mcmc_fit_accumulate(self._h)
-        if rc != 0:
-            raise RuntimeError(f"mceik_mcmc_fit_accumulate failed ({rc})")
-
-    def _fit_arrays(self):
-        nbins = self._fit_on()[1]
-        p = self.p
-        nobs, nev = len(p.tobs), p.nevents
-        return {"sq": ((nobs,), np.int64), "szq": ((nobs,), np.int64), "sq2": ((nobs, 2), np.uint64),
-                "szq2": ((nobs, 2), np.uint64), "stq": ((nev,), np.int64), "stq2": ((nev, 2), np.uint64),
-                "hist": ((max(1, p.nphase), p.nstat, nbins), np.int64), "sat": ((3,), np.int64)}
+        self._kept_accumulate(_KEPT["fit"])
 
     def fit_raw(self):
         """The accumulators as host arrays: {"n": states per chain, "tick",
@@ -1990,40 +1980,20 @@ class Sampler:
         uint64 [nobs, 2] (lo, hi words), "stq" int64 [nev], "stq2" uint64 [nev,
         2], "hist" int64 [nphase, nstat, nbins], "sat" int64 [3] (clamped q,
         zq, tq)}."""
-        tick, nbins, zmax, ref = self._fit_on()
-        out = {k: np.zeros(sh, dt) for k, (sh, dt) in self._fit_arrays().items()}
-        n = C.c_longlong(0)
-        rc = self._L.mceik_mcmc_fit_get(self._h, C.byref(n), *(out[k].ctypes.data_as(C.c_void_p) for k in out))
-        if rc != 0:
-            raise RuntimeError(f"mceik_mcmc_fit_get failed ({rc})")
-        out.update({"n": n.value, "tick": tick, "nbins": nbins, "zmax": zmax, "t0_ref": ref.copy()})
-        return out
+        return self._kept_raw(_KEPT["fit"])
 
     def _fit_set(self, raw):
-        arr = {k: np.ascontiguousarray(raw[k], dtype=dt) for k, (sh, dt) in self._fit_arrays().items()}
-        assert all(arr[k].shape == sh for k, (sh, dt) in self._fit_arrays().items())
-        rc = self._L.mceik_mcmc_fit_set(self._h, int(raw["n"]), *(arr[k].ctypes.data_as(C.c_void_p) for k in arr))
-        if rc != 0:
-            raise RuntimeError(f"mceik_mcmc_fit_set failed ({rc})")
+        self._kept_set(_KEPT["fit"], raw)
 
     def fit_partials(self):
         """The pooled sums as exact partials (`FitPartials`): what ranks exchange and merge."""
-        tick, nbins, zmax, ref = self._fit_on()
-        p = self.p
-        out = FitPartials(len(p.tobs), p.nevents, max(1, p.nphase), p.nstat, nbins, tick, zmax)
-        st = out._struct()
-        rc = self._L.mceik_mcmc_fit_partials(self._h, C.byref(st))
-        if rc != 0:
-            raise RuntimeError(f"mceik_mcmc_fit_partials failed ({rc})")
-        out.nchains, out.nkept = int(st.nchains), int(st.nkept)
-        out.sat[:] = list(st.sat)
-        return out
+        return self._kept_partials(_KEPT["fit"])
 
     def fit_last(self):
         """The last kept step's integers of every chain: (q, zq int32 [nchains,
         nobs], tq int32 [nchains, nev]); q, zq are 0 for a masked pick, rows of
         chains that are not cold stay 0."""
-        self._fit_on()
+        self._kept_on(_KEPT["fit"])
         q = np.zeros((self.nchains, len(self.p.tobs)), np.int32)
         zq, tq = np.zeros_like(q), np.zeros((self.nchains, self.p.nevents), np.int32)
         rc = self._L.mceik_mcmc_fit_last(self._h, *(a.ctypes.data_as(C.c_void_p) for a in (q, zq, tq)))
@@ -2075,13 +2045,34 @@ class Sampler:
             pass
 
 
-class PosteriorPartials:
+class _Partials:
+    """What the four *Partials share: `merge` through the C merge `_merge` of two
+    `_struct()`s (ValueError `_mismatch` where they do not match), and `_took`,
+    which copies back what a C call that filled a `_struct()` wrote into it."""
+    _merge = _mismatch = None
+
+    def _took(self, st):
+        self.nchains, self.nkept = int(st.nchains), int(st.nkept)
+
+    def merge(self, other):
+        """self += other (the C merge: mceik_posterior_merge, mceik_cov_merge,
+        mceik_ess_merge, mceik_fit_merge); both must hold the same entries,
+        options and states per chain."""
+        a, b = self._struct(), other._struct()
+        if getattr(_lib.lib(), self._merge)(C.byref(a), C.byref(b)) != 0:
+            raise ValueError(self._mismatch)
+        self._took(a)
+        return self
+
+
+class PosteriorPartials(_Partials):
     """Host arrays of mceik_posterior_partials (include/mceik.h): per model
     entry S = sum_c sum_c (int64 [ncm]), Q = sum_c sumsq_c and P = sum_c sum_c^2
     (uint64 [ncm, 2]: lo, hi words of 128 bits) and the histogram widened to
     uint64 [ncm, nbins], over `nchains` chains of `nkept` states each.  Exact
     integers: partials of shards or ranks merge by addition, in any order.
     Plain attributes, so it travels as a host object (pickle)."""
+    _merge, _mismatch = "mceik_posterior_merge", "posterior partials do not match (ncm, nbins, per_chain, nkept)"
 
     def __init__(self, ncm, nbins, per_chain, nchains=0, nkept=0, shape=None, bounds=None):
         self.ncm, self.nbins, self.per_chain = int(ncm), int(nbins), bool(per_chain)
@@ -2100,16 +2091,6 @@ class PosteriorPartials:
         st.S, st.Q, st.P = self.S.ctypes.data, self.Q.ctypes.data, self.P.ctypes.data
         st.hist = self.hist.ctypes.data if self.nbins else None
         return st
-
-    def merge(self, other):
-        """self += other (mceik_posterior_merge); both must hold the same
-        entries, bins, mode and states per chain."""
-        a, b = self._struct(), other._struct()
-        rc = _lib.lib().mceik_posterior_merge(C.byref(a), C.byref(b))
-        if rc != 0:
-            raise ValueError("posterior partials do not match (ncm, nbins, per_chain, nkept)")
-        self.nchains = int(a.nchains)
-        return self
 
     def finish(self):
         """(mean, var, rhat) float64 [ncm] (mceik_posterior_finish)."""
@@ -2192,7 +2173,7 @@ def posterior_summary(smp: Sampler, group=None, dst=0):
     return None if parts is None else PosteriorSummary(parts)
 
 
-class CovPartials:
+class CovPartials(_Partials):
     """Host arrays of mceik_cov_partials (include/mceik.h) for the probe list
     `probes` [(kind, index)]: A [np] and S [ncm] int64; G [np, np, 2], Q [ncm,
     2], C [np, ncm, 2] and, within-chain, PA, P, T of the same shapes: uint64
@@ -2200,6 +2181,7 @@ class CovPartials:
     of `nkept` states each.  Exact integers: partials of shards or ranks merge
     by addition, in any order.  Plain attributes, so it travels as a host
     object (pickle)."""
+    _merge, _mismatch = "mceik_cov_merge", "covariance partials do not match (probes, ncm, within, nkept)"
 
     def __init__(self, probes, ncm, within, nchains=0, nkept=0, shape=None):
         self.probes = [(int(k), int(i)) for k, i in probes]
@@ -2220,16 +2202,6 @@ class CovPartials:
         for name in ("A", "S", "G", "Q", "C", "PA", "P", "T"):
             setattr(st, name, getattr(self, name).ctypes.data)
         return st
-
-    def merge(self, other):
-        """self += other (mceik_cov_merge); both must hold the same probes,
-        entries, mode and states per chain."""
-        a, b = self._struct(), other._struct()
-        rc = _lib.lib().mceik_cov_merge(C.byref(a), C.byref(b))
-        if rc != 0:
-            raise ValueError("covariance partials do not match (probes, ncm, within, nkept)")
-        self.nchains = int(a.nchains)
-        return self
 
     def finish(self):
         """dict of float64 arrays (mceik_cov_finish): cov, corr, cov_within,
@@ -2287,7 +2259,7 @@ def ess_lstar(nlevels, n):
     return _lib.lib().mceik_ess_lstar(int(nlevels), int(n))
 
 
-class EssPartials:
+class EssPartials(_Partials):
     """Host arrays of mceik_ess_partials (include/mceik.h) over ne = `ncm`
     model entries + the `probes` [(kind, index)] and `nlevels` batch sizes 2^l:
     A int64 [nlevels, ne] (sum over chains of the closed level-l batch sums), Q
@@ -2296,6 +2268,7 @@ class EssPartials:
     the last close), over `nchains` chains of `nkept` states each.  Exact
     integers: partials of shards or ranks merge by addition, in any order.
     Plain attributes, so it travels as a host object (pickle)."""
+    _merge, _mismatch = "mceik_ess_merge", "batch-means partials do not match (ncm, probes, nlevels, nkept)"
 
     def __init__(self, ncm, nlevels, probes=(), nchains=0, nkept=0, shape=None):
         self.probes = [(int(k), int(i)) for k, i in probes]
@@ -2317,11 +2290,9 @@ class EssPartials:
     def merge(self, other):
         """self += other (mceik_ess_merge); both must hold the same entries,
         probes, levels and states per chain."""
-        a, b = self._struct(), other._struct()
-        if self.probes != other.probes or _lib.lib().mceik_ess_merge(C.byref(a), C.byref(b)) != 0:
-            raise ValueError("batch-means partials do not match (ncm, probes, nlevels, nkept)")
-        self.nchains = int(a.nchains)
-        return self
+        if self.probes != other.probes:  # (the C struct carries their number only)
+            raise ValueError(self._mismatch)
+        return super().merge(other)
 
     def finish(self, level=None):
         """(tau [nlevels, ne], ess [ne], mcse [ne], level) (mceik_ess_finish);
@@ -2376,7 +2347,7 @@ def fit_check(tick, rmax):
     return _lib.lib().mceik_fit_check(float(tick), float(rmax)) == 0
 
 
-class FitPartials:
+class FitPartials(_Partials):
     """Host arrays of mceik_fit_partials (include/mceik.h): sq, szq int64
     [nobs] (sums of the residuals in ticks and of 1024 z), sq2, szq2 uint64
     [nobs, 2] (lo, hi words of the 128-bit sums of their squares), stq int64
@@ -2386,6 +2357,8 @@ class FitPartials:
     t0_ref say what the rows are.  Exact integers: partials of shards or ranks
     merge by addition, in any order.  Plain attributes, so it travels as a
     host object (pickle)."""
+    _merge = "mceik_fit_merge"
+    _mismatch = "data-fit partials do not match (observations, tick, nbins, zmax, t0_ref, nkept)"
 
     def __init__(self, nobs, nev, nphase, nstat, nbins, tick, zmax, nchains=0, nkept=0):
         self.nobs, self.nev, self.nphase, self.nstat, self.nbins = int(nobs), int(nev), int(nphase), int(nstat), int(nbins)
@@ -2412,15 +2385,9 @@ class FitPartials:
             st.sat[k] = int(self.sat[k])
         return st
 
-    def merge(self, other):
-        """self += other (mceik_fit_merge); both must hold the same
-        observations, options and states per chain."""
-        a, b = self._struct(), other._struct()
-        if _lib.lib().mceik_fit_merge(C.byref(a), C.byref(b)) != 0:
-            raise ValueError("data-fit partials do not match (observations, tick, nbins, zmax, t0_ref, nkept)")
-        self.nchains = int(a.nchains)
-        self.sat[:] = list(a.sat)
-        return self
+    def _took(self, st):
+        super()._took(st)
+        self.sat[:] = list(st.sat)
 
     def finish(self):
         """dict of float64 arrays (mceik_fit_finish): pick_mean, pick_sd,

@@ -1,6 +1,8 @@
 """The kept-state hook (csrc/sampler.hip kept_queue / kept_counted) where the
-cold-chain boundary falls inside a pipe, for all five consumers at once:
-posterior, hypocentre moments, nuisance moments, covariances, batch means.
+cold-chain boundary falls inside a pipe, for six of its seven consumers at
+once: the four accumulators of csrc/kept.h (posterior, covariances, batch
+means, data fit) and the hypocentre and nuisance moments (the seventh, the
+Voronoi moments, has tests/test_gpu_vor.py).
 
 9 chains on the three-rung ladder: the cold chains are 0-2.  Two pipes split
 the chains 4 + 5, so pipe 0 holds chains 0-3, of which only 0-2 are cold, and
@@ -35,10 +37,11 @@ def _run(env, monkeypatch):
         probes = [("model", 100), ("hypo", 0, 2), ("static", 0, 1), ("noise", 0)]
         smp.cov_enable(probes, within=True)
         smp.ess_enable(3, probes=probes)
+        smp.fit_enable()
         info = smp.info()
         smp.run(NSTEPS)
         return {"info": info, "state": smp.state(), "samples": smp.samples(), "posterior": smp.posterior_raw(),
-                "cov": smp.cov_raw(), "ess": smp.ess_raw(), "hypo": smp.hypo_moments(), "nuis": smp.nuis_moments()}
+                "cov": smp.cov_raw(), "ess": smp.ess_raw(), "fit": smp.fit_raw(), "hypo": smp.hypo_moments(), "nuis": smp.nuis_moments()}
     finally:
         smp.close()
 
@@ -55,7 +58,7 @@ def test_cold_boundary_inside_a_pipe(monkeypatch):
     two = _run({"MCEIK_PIPES": "2"}, monkeypatch)
     assert one["info"]["npipe"] == 1 and two["info"]["npipe"] == 2, (one["info"], two["info"])
     assert two["info"]["chains"] == [4, 5]
-    for what in ("state", "samples", "posterior", "cov", "ess", "hypo", "nuis"):
+    for what in ("state", "samples", "posterior", "cov", "ess", "fit", "hypo", "nuis"):
         for (k, a), (k2, b) in zip(_flat(one[what]), _flat(two[what])):
             assert k == k2
             if isinstance(a, np.ndarray):
@@ -65,7 +68,7 @@ def test_cold_boundary_inside_a_pipe(monkeypatch):
     nkept = len(two["samples"][0])
     assert nkept == 11                           # kept steps 2, 4, ..., 22
     for r in (one, two):
-        assert r["posterior"]["n"] == r["cov"]["n"] == r["ess"]["n"] == nkept
+        assert r["posterior"]["n"] == r["cov"]["n"] == r["ess"]["n"] == r["fit"]["n"] == nkept
         for rows in (r["posterior"]["sum"], r["cov"]["Sc"], r["ess"]["Sc"]):
             assert rows.shape[0] == NCH and not rows[G:].any() and rows[:G].any(1).all()
         assert r["hypo"]["n"] == G * nkept and r["nuis"]["n"] == G * nkept
