@@ -125,7 +125,8 @@ __global__ void l2_gridsearch_f32_kernel(int ldgrd, int ngrd, int iwantOT, float
 // formed once per block (the same fp32 operations as l2_gridsearch_f32_kernel,
 // so every output is bitwise the same) into per-event groups aligned to 4, read
 // back as 16-B uniform (broadcast) LDS loads by the 4-way unrolled pair loops.
-// LDS: [nrows][TG] tables | per event 4-aligned (tc, w0, w1, row*TG) | offsets.
+// LDS: [nrows][TG] tables | per event 4-aligned (tc, w0, w1, row*TG) | offsets
+// | the contract flag: all of it dynamic, sized by relocate_lds_bytes.
 template <int TG>
 __global__ __launch_bounds__(TG) void relocate_lds_kernel(int ldgrd, int ngrd, int nrows, int nev, int nobs,
                                                           int iwantOT, float t0use, const int *ev_ptr,
@@ -140,9 +141,9 @@ __global__ __launch_bounds__(TG) void relocate_lds_kernel(int ldgrd, int ngrd, i
     const int cap = (nobs + 3 * nev + 3) & ~3;          // obs slots with per-event padding to 4
     float *stc = sm + (size_t)nrows * TG, *sw0 = stc + cap, *sw1 = sw0 + cap;
     int *srow = (int *)(sw1 + cap), *soff = srow + cap;    // soff [nev + 1]
+    int &bad = soff[nev + 1];                           // the caller's nobs / nrows do not hold
     const float sqrt2i = 0.7071067811865475f;
     const int tid = threadIdx.x;
-    __shared__ int bad;                                 // the caller's nobs / nrows do not hold
     if (tid == 0) {
         int o = 0, b = ev_ptr[0] != 0 || ev_ptr[nev] != nobs;
         for (int e = 0; e < nev && !b; e++) {
@@ -350,10 +351,14 @@ hipError_t l2_gridsearch(int ldgrd, int ngrd, int nuse, int iwantOT, double t0us
     return hipGetLastError();
 }
 
+// All the LDS relocate_lds_kernel uses: the tables, the observation groups, the
+// nev + 1 group offsets and the contract flag.  The kernel declares no static
+// LDS (its code object's .group_segment_fixed_size is 0), so this is what a
+// launch asks for and what mceik_relocate holds against its 64 KiB budget.
 #define RELOC_TG 256
 size_t relocate_lds_bytes(int nrows, int nobs, int nev)
 {
-    return (size_t)nrows * RELOC_TG * 4 + (size_t)((nobs + 3 * nev + 3) & ~3) * 16 + (size_t)(nev + 1) * 4;
+    return (size_t)nrows * RELOC_TG * 4 + (size_t)((nobs + 3 * nev + 3) & ~3) * 16 + (size_t)(nev + 2) * 4;
 }
 
 hipError_t relocate_lds(int ldgrd, int ngrd, int nrows, int nev, int nobs, int iwantOT, float t0use,

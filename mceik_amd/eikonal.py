@@ -135,7 +135,7 @@ def locate_l2_gridsearch_f32(ldgrd, ngrd, nobs, iwantOT, t0use, mask, tobs, tcor
 
 
 def relocate(tables, events, ldgrd=None, iwantOT=1, t0use=0.0, log_pdf=True, stream=0, single_pass=True,
-             want_t0=True, norm=2):
+             want_t0=True, norm=2, ngrd=None):
     """Relocation grid search (SURVEY s.8f row 2) of many events against one
     model's travel-time tables, one GPU launch (mceik_relocate).
 
@@ -144,6 +144,11 @@ def relocate(tables, events, ldgrd=None, iwantOT=1, t0use=0.0, log_pdf=True, str
     events : list of dicts with 'rows' (int table row of each observation),
              'tobs', 'varobs', optional 'tcorr' and 'mask' (1 = masked),
              in the reference's observation order
+    ldgrd  : the leading dimension of the tables and of both results (default:
+             the tables' row length); without `ngrd` also the number of grid
+             points searched
+    ngrd   : the number of grid points searched, 1 <= ngrd <= ldgrd; columns
+             [ngrd, ldgrd) of every result row are left unwritten
     returns (out, t0): torch float32 [nev, ldgrd]; out = -objfn if log_pdf
     else objfn (locate.c L2 with the analytic origin time, fp32).
     norm=1: the L1 objective with the weighted-median origin time and the raw
@@ -156,6 +161,8 @@ def relocate(tables, events, ldgrd=None, iwantOT=1, t0use=0.0, log_pdf=True, str
     dev = tables.device
     nrows, ld = tables.shape
     ld = ldgrd or ld
+    if ngrd is not None and not 1 <= int(ngrd) <= ld:
+        raise ValueError("ngrd: 1 <= ngrd <= ldgrd")
     ptr, rows, tc, wt, xn = [0], [], [], [], []
     for ev in events:
         m = np.zeros(len(ev["rows"]), np.int32) if ev.get("mask") is None else np.asarray(ev["mask"])
@@ -181,7 +188,7 @@ def relocate(tables, events, ldgrd=None, iwantOT=1, t0use=0.0, log_pdf=True, str
     b = _lib.RelocateBatch()
     b.ldgrd, b.ngrd, b.nev, b.iwantOT, b.t0use = ld, int(tables.shape[1]) if ldgrd is None else int(ldgrd), nev, \
         int(iwantOT), float(t0use)
-    b.ngrd = min(b.ngrd, ld)
+    b.ngrd = min(b.ngrd, ld) if ngrd is None else int(ngrd)
     b.tables, b.ev_ptr, b.obs_row = tables.data_ptr(), d_ptr.data_ptr(), d_rows.data_ptr()
     b.tc, b.wt, b.xnorm = d_tc.data_ptr(), d_wt.data_ptr(), d_xn.data_ptr()
     b.t0, b.out, b.log_pdf = (t0.data_ptr() if want_t0 else None), out.data_ptr(), 1 if log_pdf else 0
